@@ -18,7 +18,14 @@ then [N > 1: one all-reduce of the partial class stacks] and the f-v image of ev
 and the trajectories are resident before the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload synth10k|weights|speeds|sliding|timelapse]
-                    [--scaling weak|strong|both]
+                    [--scaling weak|strong|both] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything else the
+bench measures or checks after the timed steps: the CPU baseline (unless --no-cpu-baseline), the dominant
+kernel's roofline bookkeeping and PMC lookups, the parity checks against the oracle and the separately timed
+launches (bootstrap's f-v launch, speeds-host's H2D rate).  --dump-outputs DIR writes what the last timed step
+computed (the arrays its caller receives) as DIR/<name>.npy; the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 
 weak (default at N = 1): every rank images its own full job (value = N x the job per step).  strong:
 ONE job of the configured size is split over the ranks (das_diff_veh_amd.distributed.shard_passes:
@@ -64,7 +71,13 @@ def parse_args(argv=None):
     ap.add_argument("--scaling", default=None, choices=("weak", "strong", "both"),
                     help="weak: every rank its own job; strong: one job split over the ranks; both (default for "
                          "N > 1): the weak line with the strong (fixed-job) measurement beside it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baseline, roofline bookkeeping, parity "
+                         "checks against the oracle, separately timed launches")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (float32 / float64; a "
+                         "fixed seeded sample of an output above the size cap)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--chunk", type=int, default=8, help="passes per stack task (one wave, one gather row)")
     ap.add_argument("--pool", type=int, default=None, help="resident windows (= passes per stack launch) of the pool "
@@ -240,6 +253,29 @@ WORKLOADS = {
 def log(*a):
     if int(os.environ.get("RANK", "0")) == 0:
         print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_CAP_BYTES = 48 << 20  # all of a run's dumped arrays together stay well under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> device tensor or NumPy array, the last timed step's outputs) as
+    out_dir/<name>.npy in float32 (float64 stays float64).  The arrays share DUMP_CAP_BYTES equally; one above
+    its share is written as a fixed sample of its flattened elements (ascending indices drawn with seed 0, the
+    same from run to run), so the same positions are compared between two builds."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        a = a.detach()
+        if a.dtype != torch.float64:
+            a = a.float()
+        k = share // a.element_size()
+        if a.numel() > k:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.numel(), k))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
 
 
 def tercile_slots(speeds):
@@ -825,11 +861,13 @@ def timelapse_main(args, world, rank, device):
         elapsed = max_over_ranks(elapsed, device)
     t = np.array([[e[i].elapsed_time(e[i + 1]) for i in range(3)] for e in evs]).mean(axis=0) / 1e3  # s
 
-    # parity: two images against the oracle (after timing)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"fv": fv})
+    # --full: parity, two images against the oracle (after timing)
     from oracle import disp as odisp
-    host = data.double().cpu().numpy()
+    host = data.double().cpu().numpy() if args.full else None
     errs, picks = [], []
-    for b in (0, B - 1):
+    for b in ((0, B - 1) if args.full else ()):
         ref = odisp.map_fv(host[b], dx, dt, freqs, vels)
         got = fv[b].double().cpu().numpy()
         errs.append(float(np.abs(got - ref).max() / np.abs(ref).max()))
@@ -872,11 +910,12 @@ def timelapse_main(args, world, rank, device):
         "kernels_ms": {"time_dft": t[0] * 1e3, "fk_contract": t[1] * 1e3, "fv": t[2] * 1e3},
         "time_dft_mfma_frac": tdft_flop / t[0] / 1e12 / FP64_MFMA_SPEC_TF,
         "time_dft_mfma_frac_of_measured_ceiling": tdft_flop / t[0] / 1e12 / FP64_MFMA_PEAK_TF,
-        "parity": {"max_rel_err": max(errs), "picks_ok": all(picks), "images_checked": 2, "tol": 1e-4},
+        "parity": {"max_rel_err": max(errs), "picks_ok": all(picks), "images_checked": 2, "tol": 1e-4} if args.full
+        else None,
         "host_setup_s": t_setup,
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # the oracle's map_fv (fft2, FITPACK bilinear via RectBivariateSpline, savgol) on one core over a
         # bounded sample of the same gathers, then on every usable core at once (oracle/cpu_legs.py fv)
         budget = args.cpu_budget / 2
@@ -905,6 +944,28 @@ def timelapse_main(args, world, rank, device):
 
 
 FP64_VALU_SPEC_TF = 78.6  # MI355X spec sheet, FP64 vector
+
+
+def prep_parity(rec, out, dt):
+    """--full, after timing: the step's output against the reference's own path on the whole record
+    (scipy.signal.sosfiltfilt as bandpass_data calls it, then the imputation and norm), and the bandpass
+    of two traces against the oracle's pure-Python sosfiltfilt restatement (pinned by tests/golden/prep.npz).
+    Returns the parity record and the host copy of the record."""
+    from das_diff_veh_amd.preprocess import bandpass_inplace
+    from oracle import preprocess as oprep
+    host = rec.cpu().numpy()
+    ref = oprep.surface_wave_prep(host, dt, scipy_filter=True)
+    got = out.double().cpu().numpy()
+    err = float(np.abs(got - ref).max() / np.abs(ref).max())
+    bp_dev = rec[[0, 700]].double().clone()
+    bandpass_inplace(bp_dev, dt, 1.2, 30)
+    bp_ref = oprep.bandpass_data(host[[0, 700]], dt, 1.2, 30)
+    err_bp = float(np.abs(bp_dev.cpu().numpy() - bp_ref).max() / np.abs(bp_ref).max())
+    return {"max_rel_err": err, "tol": 2e-6,
+            "reference": "oracle/preprocess.py surface_wave_prep(scipy_filter=True): scipy.signal.sosfiltfilt as "
+                         "bandpass_data calls it, imputation and norm in float64, on the whole record",
+            "bandpass_rel_err_vs_restatement": err_bp, "bandpass_tol": 1e-10,
+            "bandpass_check": "traces 0 and 700 in float64 against oracle/preprocess.py's pure-Python sosfiltfilt"}, host
 
 
 def prep_main(args, world, rank, device):
@@ -957,19 +1018,11 @@ def prep_main(args, world, rank, device):
     n_tiles = n_ch * (-(-n_ext // 64)) / 16.0
     mfma_flop = n_tiles * (32 + 92 + 60) * 2.0 * 16 * 16 * 4
     rec_bytes = 4.0 * n_ch * n_t
-    # parity (after timing): the step's output against the reference's own path on the whole record
-    # (scipy.signal.sosfiltfilt as bandpass_data calls it, then the imputation and norm), and the bandpass
-    # of two traces against the oracle's pure-Python sosfiltfilt restatement (pinned by tests/golden/prep.npz)
-    from das_diff_veh_amd.preprocess import bandpass_inplace
-    from oracle import preprocess as oprep
-    host = rec.cpu().numpy()
-    ref = oprep.surface_wave_prep(host, dt, scipy_filter=True)
-    got = out.double().cpu().numpy()
-    err = float(np.abs(got - ref).max() / np.abs(ref).max())
-    bp_dev = rec[[0, 700]].double().clone()
-    bandpass_inplace(bp_dev, dt, 1.2, 30)
-    bp_ref = oprep.bandpass_data(host[[0, 700]], dt, 1.2, 30)
-    err_bp = float(np.abs(bp_dev.cpu().numpy() - bp_ref).max() / np.abs(bp_ref).max())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"record": out})
+    parity = None
+    if args.full:
+        parity, host = prep_parity(rec, out, dt)
     res = {
         "metric": "continuous-record preprocessing: records/s (_preprocessing_for_surface_waves, 1,024 ch x 60 s); "
                   "% FP64 roofline of the bandpass",
@@ -994,17 +1047,14 @@ def prep_main(args, world, rank, device):
                      "hbm_bytes_model": "record read + y (f64) written and read + record written",
                      "hbm_frac": (2 * rec_bytes + 16.0 * n_ch * n_ext) / bp / 1e9 / HBM_PEAK_GBS},
         "kernels_ms": {"bandpass": bp * 1e3, "trace_cleanup": cl * 1e3},
-        "parity": {"max_rel_err": err, "tol": 2e-6,
-                   "reference": "oracle/preprocess.py surface_wave_prep(scipy_filter=True): scipy.signal.sosfiltfilt as "
-                                "bandpass_data calls it, imputation and norm in float64, on the whole record",
-                   "bandpass_rel_err_vs_restatement": err_bp, "bandpass_tol": 1e-10,
-                   "bandpass_check": "traces 0 and 700 in float64 against oracle/preprocess.py's pure-Python sosfiltfilt"},
+        "parity": parity,
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # the oracle (scipy's sosfiltfilt + the reference's imputation / norm) on one core, on trace slices of the
         # same record for ~cpu_budget / 2 s, scaled to the full record; then every usable core at once, each worker
         # on its own 64-trace slice (oracle/cpu_legs.py prep)
+        from oracle import preprocess as oprep
         torch.set_num_threads(1)
         sub = host[:128]
         n, t_c = 0, time.time()
@@ -1032,6 +1082,34 @@ def prep_main(args, world, rank, device):
         dist.destroy_process_group()
 
 
+def fv_launch_roofline(cache, plan, B):
+    """--full: the bootstrap step's f-v launch alone (its dominant kernel), timed on its stream after the timed
+    steps over a batch of the same size, against the FP64 MFMA peak."""
+    from das_diff_veh_amd import bootstrap as bt
+    from das_diff_veh_amd.disp import _use_mfma
+    mfma = _use_mfma(plan, B)
+    stacks = cache.resample_stacks(np.tile(np.arange(1, 31, dtype=np.int32), (B, 1)))
+    FK = bt.fk_grid(stacks, plan)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(2):
+        bt.fv_from_fk(FK, plan)
+    reps = 5
+    e0.record()
+    for _ in range(reps):
+        bt.fv_from_fk(FK, plan)
+    e1.record()
+    torch.cuda.synchronize()
+    t_fv = e0.elapsed_time(e1) / reps / 1e3
+    n_tiles = -(-(plan.nF - 16) // 16) + 1
+    mfma_flop = 2.0 * 16 * 16 * 40 * n_tiles * B * -(-plan.nV // 16)
+    achieved = (mfma_flop if mfma else 2.0 * 25 * B * plan.nV * plan.nF) / t_fv / 1e12
+    return {"bound": "mfma", "achieved": achieved, "peak": FP64_MFMA_SPEC_TF, "unit": "TFLOP/s",
+            "frac": achieved / FP64_MFMA_SPEC_TF, "frac_of_measured_ceiling": achieved / FP64_MFMA_PEAK_TF,
+            "traffic": None, "kernel": "fv_mfma_kernel" if mfma else "fv_kernel", "launch_ms": t_fv * 1e3,
+            "flop_model": "10 v_mfma_f64_16x16x4_f64 per (16 v x 16 f) tile" if mfma else "25-tap FIR",
+            "hbm_frac": 4.0 * B * plan.nV * plan.nF / t_fv / 1e9 / HBM_PEAK_GBS}
+
+
 def bootstrap_main(args, world, rank, device):
     """one step = the notebook's convergence_test for one class (gathers of the class's
     resident windows, then bt_size 1..60 x 30 resamples through one dispersion batch and 4 ridges).  Classes
@@ -1040,7 +1118,6 @@ def bootstrap_main(args, world, rank, device):
     import random
 
     from das_diff_veh_amd import bootstrap as bt
-    from das_diff_veh_amd.disp import _use_mfma
     from das_diff_veh_amd.plan import pack_trajectories
     import scipy.interpolate
     wl = WORKLOADS["bootstrap"]
@@ -1082,23 +1159,9 @@ def bootstrap_main(args, world, rank, device):
         span("select1", "disp1"), span("disp1", "ridge1")
     _, _, plan = cache.disp_plan()
     B = S * T
-    mfma = _use_mfma(plan, B)
-    # the f-v launch alone (dominant kernel): time it on its stream after the timed steps, same batch
-    stacks = cache.resample_stacks(np.tile(np.arange(1, 31, dtype=np.int32), (B, 1)))
-    FK = bt.fk_grid(stacks, plan)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(2):
-        bt.fv_from_fk(FK, plan)
-    reps = 5
-    e0.record()
-    for _ in range(reps):
-        bt.fv_from_fk(FK, plan)
-    e1.record()
-    torch.cuda.synchronize()
-    t_fv = e0.elapsed_time(e1) / reps / 1e3
-    n_tiles = -(-(plan.nF - 16) // 16) + 1
-    mfma_flop = 2.0 * 16 * 16 * 40 * n_tiles * B * -(-plan.nV // 16)
-    achieved = (mfma_flop if mfma else 2.0 * 25 * B * plan.nV * plan.nF) / t_fv / 1e12
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"std": std})
+    roofline = fv_launch_roofline(cache, plan, B) if args.full else None
     res = {
         "metric": "bootstrap convergence_test: resamples/s (one class, bt_size 1..60 x 30, 4 ridge modes); % MFMA "
                   "roofline of the f-v kernel",
@@ -1113,15 +1176,11 @@ def bootstrap_main(args, world, rank, device):
         "step_breakdown_ms": {"gathers_and_host_draws": t_gather * 1e3, "resample_stacks": t_sel * 1e3,
                               "dispersion": t_disp * 1e3, "ridges": t_ridge * 1e3,
                               "host_draws": float(np.mean([e["draw_host_s"] for e in evs])) * 1e3},
-        "roofline": {"bound": "mfma", "achieved": achieved, "peak": FP64_MFMA_SPEC_TF, "unit": "TFLOP/s",
-                     "frac": achieved / FP64_MFMA_SPEC_TF, "frac_of_measured_ceiling": achieved / FP64_MFMA_PEAK_TF,
-                     "traffic": None, "kernel": "fv_mfma_kernel" if mfma else "fv_kernel", "launch_ms": t_fv * 1e3,
-                     "flop_model": "10 v_mfma_f64_16x16x4_f64 per (16 v x 16 f) tile" if mfma else "25-tap FIR",
-                     "hbm_frac": 4.0 * B * plan.nV * plan.nF / t_fv / 1e9 / HBM_PEAK_GBS},
+        "roofline": roofline,
         "std_sum_mode0_first_last": [float(std[0, 0]), float(std[0, -1])],
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # the reference's bootstrap_disp recomputes every gather of every resample: its cost per resample of
         # size k is k VSG gathers + one f-v image + 4 ridges; timed with the oracle on one core (gather, f-v
         # image, ridge) on the bench's own windows, then priced over the step's 1,800 resamples
@@ -1182,6 +1241,19 @@ def bootstrap_main(args, world, rank, device):
         dist.destroy_process_group()
 
 
+def h2d_rate(device):
+    """--full: the H2D rate (GB/s) of pinned 64 MB copies measured in this run (the bound of a host-fed step)."""
+    pin = torch.empty(64 << 20, dtype=torch.uint8, pin_memory=True)
+    dst = torch.empty(64 << 20, dtype=torch.uint8, device=device)
+    dst.copy_(pin, non_blocking=True)
+    torch.cuda.synchronize()
+    ta = time.perf_counter()
+    for _ in range(10):
+        dst.copy_(pin, non_blocking=True)
+    torch.cuda.synchronize()
+    return 10 * (64 << 20) / (time.perf_counter() - ta) / 1e9
+
+
 def host_main(args, world, rank, device):
     """The drop-in classes fed from host memory (imaging_diff_speed.ipynb's get_images calls): one step = the
     three classes' get_images on NumPy windows, their H2D staging (device.stage_windows: pinned double
@@ -1231,16 +1303,9 @@ def host_main(args, world, rank, device):
         elapsed = max_over_ranks(elapsed, device)
     step_s = elapsed / args.steps
     win_bytes = 4.0 * n * n_ch * n_t
-    # the H2D rate of a pinned 64 MB copy on this box (the bound of a host-fed step)
-    pin = torch.empty(64 << 20, dtype=torch.uint8, pin_memory=True)
-    dst = torch.empty(64 << 20, dtype=torch.uint8, device=device)
-    dst.copy_(pin, non_blocking=True)
-    torch.cuda.synchronize()
-    ta = time.perf_counter()
-    for _ in range(10):
-        dst.copy_(pin, non_blocking=True)
-    torch.cuda.synchronize()
-    h2d = 10 * (64 << 20) / (time.perf_counter() - ta) / 1e9
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {f"xcf_class{c}": x for c, x in enumerate(res_imgs)})
+    h2d = h2d_rate(device) if args.full else None
     res = {
         "metric": "host-fed vehicle-pass windows/sec (drop-in get_images on NumPy windows, H2D included)",
         "value": world * n / step_s, "unit": "vehicle-pass windows/s", "n_gpus": world, "steps": args.steps,
@@ -1252,7 +1317,7 @@ def host_main(args, world, rank, device):
         "roofline": {"bound": "pcie", "achieved": win_bytes / step_s / 1e9, "peak": h2d, "unit": "GB/s",
                      "frac": win_bytes / step_s / 1e9 / h2d, "traffic": None,
                      "peak_source": "pinned 64 MB H2D copies measured in this run (PCIe Gen5 x16 spec 63 GB/s)",
-                     "pcie_bound_windows_per_s": h2d * 1e9 / (4.0 * n_ch * n_t)},
+                     "pcie_bound_windows_per_s": h2d * 1e9 / (4.0 * n_ch * n_t)} if args.full else None,
         "avg_image_finite": bool(all(np.isfinite(x).all() for x in res_imgs)),
         "cpu_baseline": None,
     }
@@ -1317,22 +1382,24 @@ def main():
         WORKLOADS[args.workload]["t0"] = DT_W499
     scaling = args.scaling or ("weak" if world == 1 else "both")
     res = measure(args, "strong" if scaling == "strong" else "weak", world, rank, device,
-                  cpu=rank == 0 and world == 1 and not args.no_cpu_baseline)
+                  cpu=rank == 0 and world == 1 and args.full and not args.no_cpu_baseline,
+                  dump=args.dump_outputs if rank == 0 else None)
     if scaling == "both":
         # the fixed job of the configured size split over the ranks, measured beside the weak line
         strong = measure(args, "strong", world, rank, device, cpu=False)
         res["strong_scaling"] = {k: strong[k] for k in ("value", "ms_per_step", "scaling")}
         res["strong_scaling"].update({k: strong["config"][k] for k in ("windows_per_step", "windows_per_step_this_rank")})
-        res["strong_scaling"]["stack_launch_ms"] = strong["roofline"]["launch_ms"]
+        res["strong_scaling"]["stack_launch_ms"] = strong["stack_launch_ms"]
     if rank == 0:
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
 
-def measure(args, scaling, world, rank, device, cpu):
+def measure(args, scaling, world, rank, device, cpu, dump=None):
     """Build the workload's job for `scaling`, time args.steps steps after args.warmup, and return the
-    result record (rank 0's view, elapsed = max over ranks)."""
+    result record (rank 0's view, elapsed = max over ranks).  dump: directory for the last step's class
+    stacks and f-v images (--dump-outputs)."""
     job = build(args.workload, device, world, rank, scaling, chunk=args.chunk)
     torch.cuda.synchronize()
     log(f"[bench] rank {rank}: {job.windows.shape[0]} resident windows generated in {job.t_gen:.2f}s, host setup "
@@ -1345,12 +1412,12 @@ def measure(args, scaling, world, rank, device, cpu):
     for _ in range(args.warmup):
         step(job, world, fused=not args.separate_validity)
     torch.cuda.synchronize()
-    # algorithmic bytes of every stack launch (bookkeeping outside the timed region: a batch whose
+    # --full: algorithmic bytes of every stack launch (bookkeeping outside the timed region: a batch whose
     # tables share a buffer with others is re-derived first; each batch's tables are copied back once)
     fused = [bool(not args.separate_validity and b.validity and (b.plan.flags & 6)) for b in job.batches]
     corr_bytes, win_bytes = [], []
     out_bytes = 4 * job.stack.shape[0] * job.stack.shape[1] * job.stack.shape[2]
-    for b in job.batches:
+    for b in (job.batches if args.full else ()):
         if b.derive:
             b.plan.derive()
         corr_bytes.append(b.plan.algorithmic_bytes(out_rows=job.stack.shape[0] * job.stack.shape[1]))
@@ -1381,14 +1448,10 @@ def measure(args, scaling, world, rank, device, cpu):
           for p in PHASES}
     windows_per_step = job.n_global
     images_per_step = job.stack.shape[0]
-    # roofline of the dominant kernel (vsg_stack): algorithmic bytes per launch / mean launch time
-    bytes_per_launch = float(np.mean(bytes_stack))
     launch_s = float(ms["stack"].mean()) / 1e3
-    achieved = bytes_per_launch / launch_s / 1e9
-    layout = layout_of(job, args, scaling)
-    kname = "vsg_stackv_kernel" if all(fused) else "vsg_stackf_kernel"
-    traffic, traffic_src = pmc_lookup(kname, layout, "traffic_bytes")
     step_ms = elapsed / args.steps * 1e3
+    if dump:
+        dump_outputs(dump, {"stack": job.stack, "fv": job.fv})
     res = {
         "metric": "vehicle-pass windows/sec -> stacked VSG + f-v images/sec; % HBM/MFMA roofline",
         "value": windows_per_step * args.steps / elapsed,
@@ -1410,30 +1473,39 @@ def measure(args, scaling, world, rank, device, cpu):
                    "chunk": args.chunk, "gather_units_per_step_this_rank": job.units, "stack_launches_per_step": nb},
         "images_per_s": images_per_step * args.steps / elapsed,
         "gather_units_per_s": job.units * (job.n_global / job.n_local) * args.steps / elapsed,
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "kernel": "vsg_stackv_kernel" if all(fused) else "vsg_stackf_kernel",
-                     "bytes_per_launch": bytes_per_launch, "launch_ms": launch_s * 1e3,
-                     "bytes_model": "every window sample once + stack rows written (validity read fused into the "
-                                    "launch)" if all(fused) else "receiver samples under sub-windows + distinct pivot "
-                                    "samples + stack rows written",
-                     "correlation_bytes_per_launch": float(np.mean(corr_bytes)),
-                     "correlation_frac": float(np.mean(corr_bytes)) / launch_s / 1e9 / HBM_PEAK_GBS},
+        "roofline": None,
+        "stack_launch_ms": launch_s * 1e3,
         "step_breakdown_ms": {p: float(ms[p].sum(axis=1).mean()) for p in PHASES},
         "host_setup_s": job.t_plan,
     }
     res["step_breakdown_ms"]["fv_allreduce_rest"] = step_ms - sum(res["step_breakdown_ms"].values())
-    if any(win_bytes) and not any(fused):
-        vs = float(ms["validity"].mean()) / 1e3
-        res["validity_roofline"] = {"kernel": "window_sumsq_kernel", "bytes_per_launch": float(np.mean(win_bytes)),
-                                    "launch_ms": vs * 1e3, "achieved": float(np.mean(win_bytes)) / vs / 1e9,
-                                    "frac": float(np.mean(win_bytes)) / vs / 1e9 / HBM_PEAK_GBS}
-    valu, valu_src = pmc_lookup(kname, layout, "SQ_INSTS_VALU")
-    res["valu_roofline"] = {"achieved": None if valu is None else valu / launch_s, "peak": VALU_PEAK_INSTR_S,
-                            "unit": "wave-instr/s", "frac": None if valu is None else valu / launch_s / VALU_PEAK_INSTR_S,
-                            "instr_per_launch": valu, "source": valu_src, "clock_assumed_ghz": 2.4,
-                            "model": "wave64 VALU instruction = 2 cycles on a SIMD-32 (>= 2 waves per SIMD) at the "
-                                     "2.4 GHz max clock"}
+    if args.full:
+        # roofline of the dominant kernel (vsg_stack): algorithmic bytes per launch / mean launch time
+        bytes_per_launch = float(np.mean(bytes_stack))
+        achieved = bytes_per_launch / launch_s / 1e9
+        layout = layout_of(job, args, scaling)
+        kname = "vsg_stackv_kernel" if all(fused) else "vsg_stackf_kernel"
+        traffic, traffic_src = pmc_lookup(kname, layout, "traffic_bytes")
+        res["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                           "kernel": kname, "bytes_per_launch": bytes_per_launch, "launch_ms": launch_s * 1e3,
+                           "bytes_model": "every window sample once + stack rows written (validity read fused into "
+                                          "the launch)" if all(fused) else "receiver samples under sub-windows + "
+                                          "distinct pivot samples + stack rows written",
+                           "correlation_bytes_per_launch": float(np.mean(corr_bytes)),
+                           "correlation_frac": float(np.mean(corr_bytes)) / launch_s / 1e9 / HBM_PEAK_GBS}
+        if any(win_bytes) and not any(fused):
+            vs = float(ms["validity"].mean()) / 1e3
+            res["validity_roofline"] = {"kernel": "window_sumsq_kernel", "bytes_per_launch": float(np.mean(win_bytes)),
+                                        "launch_ms": vs * 1e3, "achieved": float(np.mean(win_bytes)) / vs / 1e9,
+                                        "frac": float(np.mean(win_bytes)) / vs / 1e9 / HBM_PEAK_GBS}
+        valu, valu_src = pmc_lookup(kname, layout, "SQ_INSTS_VALU")
+        res["valu_roofline"] = {"achieved": None if valu is None else valu / launch_s, "peak": VALU_PEAK_INSTR_S,
+                                "unit": "wave-instr/s",
+                                "frac": None if valu is None else valu / launch_s / VALU_PEAK_INSTR_S,
+                                "instr_per_launch": valu, "source": valu_src, "clock_assumed_ghz": 2.4,
+                                "model": "wave64 VALU instruction = 2 cycles on a SIMD-32 (>= 2 waves per SIMD) at the "
+                                         "2.4 GHz max clock"}
     if cpu and (job.cpu_sets or getattr(job, "cpu_units", None)):
         cb = cpu_baseline(job, args.cpu_budget) if job.cpu_sets else cpu_baseline_sliding(job, args.cpu_budget)
         res["cpu_baseline"] = cb

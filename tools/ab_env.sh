@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for r in 1 2; do
   for k in "${!vars[@]}"; do
     out=gpurun_out/ab_${tag}_${k}_$r.json
-    env ${vars[$k]} timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > "$out" 2> "${out%.json}.err" \
+    env ${vars[$k]} timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > "$out" 2> "${out%.json}.err" \
       || { echo "variant $k failed"; tail -5 "${out%.json}.err"; exit 1; }
     python - "$out" "${vars[$k]}" << 'PY'
 import json, sys

@@ -30,7 +30,7 @@ run_tests() {
 
 bench_line() {  # out-file, bench args...
   local out=$1; shift
-  timeout -k 10 600 python bench.py "$@" > "$out" 2> "${out%.json}.err" || { tail -5 "${out%.json}.err"; return 1; }
+  timeout -k 10 600 python bench.py --full "$@" > "$out" 2> "${out%.json}.err" || { tail -5 "${out%.json}.err"; return 1; }
   python - "$out" << 'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
