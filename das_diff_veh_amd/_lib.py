@@ -52,6 +52,9 @@ SIGNATURES = {
     "dvh_cut_windows": [_p, _i32, _i64, _i64, _i64, _p, _i32, _i64, _i32, _i32, _p, _i32, _p, _p],
     "dvh_mute_traj": [_p, _i32, _i32, _i64, _i32, _i32, _p, _p, _p],
     "dvh_mute_time": [_p, _i32, _i64, _i32, _p, _p],
+    "dvh_median_abs_gate": [_p, _i32, _i64, _i64, _i32, _f64, _p, _p, _p],
+    "dvh_resample_rows_t": [_p, _i32, _i32, _i64, _i32, _i32, _p, _i32, _i32, _i32, _p, _i64, _i32, _p],
+    "dvh_transpose_f64": [_p, _i64, _i64, _i64, _p, _i64, _p],
 }
 _RESTYPES = {"dvh_last_error": C.c_char_p, "dvh_vsg_stack_workspace": C.c_int64, "dvh_sosfiltfilt_workspace": C.c_int64,
              "dvh_sosfiltfilt_plan_bytes": C.c_int64, "dvh_sos_pole_radius": C.c_double}

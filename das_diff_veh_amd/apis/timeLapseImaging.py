@@ -1,24 +1,36 @@
-"""TimeLapseImaging — the imaging half of apis/timeLapseImaging.py:22-211 on the device.
+"""TimeLapseImaging — apis/timeLapseImaging.py:22-211 on the device, without the tracker itself.
 
 Mirrors the reference class's constructor, attributes and imaging methods:
   _preprocessing_for_surface_waves  :50-71   bandpass + empty / noisy trace imputation + trace norm
                                              (preprocess.surface_wave_preprocessing, dvh_sosfiltfilt,
                                              dvh_trace_cleanup)
+  preprocess_for_tracking           :73-104  _preprocess_for_tracking: median gate, imputation, 0.08-1 Hz
+                                             bandpass, 204/25 resampling onto the 1 m x 50 Hz tracking grid,
+                                             spatial bandpass (preprocess.tracking_preprocessing,
+                                             dvh_median_abs_gate, dvh_resample_rows_t, dvh_transpose_f64)
   select_surface_wave_windows       :166-196 SurfaceWaveSelector on data_for_imaging (sw_selector)
                                              and on the raw data (qs_selector), cut on the device
   get_images                        :198-201 DispersionImagesFromWindows (flavour B) or
                                              VirtualShotGathersFromWindows (xcorr) of sw_selector
   save_avg_disp_to_npz              :205-206
-Vehicle tracking (_preprocess_for_tracking :73-104, track_cars :106-120: KF_tracking of
-apis/tracking.py) is outside the device hot path: the constructor skips it and the
-tracking results (veh_states on the 1 m / 50 Hz tracking grid) are attached with ``set_tracking``,
-e.g. from the reference's own tracker or from stored tracks.
+The tracker (track_cars :106-120: find_peaks, the detection likelihood and the Kalman loop of KF_tracking,
+apis/tracking.py) is sequential host work outside the device hot path and stays external.
+The constructor skips the tracking preprocessing (unlike the reference's); the flow from a raw record is
+
+  obj = TimeLapseImaging(data, x_axis, t_axis)
+  obj.preprocess_for_tracking()                      # data_for_tracking, dist_along_fiber_tracking, t_axis_tracking
+  veh_states = <external tracker>(obj.data_for_tracking[start_idx:end_idx + 1:3], ...)
+  obj.set_veh_states(veh_states, start_x)            # tracks on the grid left by preprocess_for_tracking
+  obj.select_surface_wave_windows(x0)
+
+Tracks made elsewhere, with their own grid (e.g. the reference's tracker run on the CPU, or stored tracks),
+are attached with ``set_tracking`` instead.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from ..preprocess import surface_wave_preprocessing
+from ..preprocess import surface_wave_preprocessing, tracking_preprocessing
 from .data_classes import SurfaceWaveSelector
 from .imaging_classes import DispersionImagesFromWindows, VirtualShotGathersFromWindows
 
@@ -51,6 +63,15 @@ class TimeLapseImaging:
             self.data, self.dt, method=self.method, flo=flo, fhi=fhi, impute_noise_traces=impute_noise_traces,
             noise_threshold=noise_threshold, impute_empty_traces=impute_empty_traces)
 
+    def preprocess_for_tracking(self, subsamp_factor=5, noise_level=10, channel0=400):
+        """_preprocess_for_tracking (:74-102) on the device; explicit, the constructor does not call it."""
+        d = self.tracking_preprecessing_dict
+        self.data_for_tracking, self.dist_along_fiber_tracking, step = tracking_preprocessing(
+            self.data, self.dt, self.x_axis[0], flo=d.get("flo", 0.08), fhi=d.get("fhi", 1),
+            flo_space=d.get("flo_space", 0.006), fhi_space=d.get("fhi_space", 0.04), subsamp_factor=subsamp_factor,
+            noise_level=noise_level, channel0=channel0)
+        self.t_axis_tracking = self.t_axis[::step]
+
     def set_tracking(self, veh_states, start_x, dist_along_fiber_tracking, t_axis_tracking, end_x=None):
         """The attributes track_cars / _preprocess_for_tracking leave behind (:73-120)."""
         self.veh_states = np.asarray(veh_states)
@@ -58,6 +79,15 @@ class TimeLapseImaging:
         self.end_x = end_x
         self.dist_along_fiber_tracking = np.asarray(dist_along_fiber_tracking)
         self.t_axis_tracking = np.asarray(t_axis_tracking)
+
+    def set_veh_states(self, veh_states, start_x, end_x=None):
+        """The attributes track_cars leaves behind (:105-119), for tracks made on the grid of
+        preprocess_for_tracking."""
+        if not hasattr(self, "dist_along_fiber_tracking") or not hasattr(self, "t_axis_tracking"):
+            raise AttributeError("no tracking grid: call preprocess_for_tracking() first (or set_tracking())")
+        self.veh_states = np.asarray(veh_states)
+        self.start_x = start_x
+        self.end_x = end_x
 
     def track_cars(self, *args, **kwargs):
         raise NotImplementedError("vehicle tracking (KF_tracking, apis/tracking.py) is outside the device hot path; "

@@ -9,6 +9,10 @@
   mute_along_time   apis/data_classes.py:100-104 -> dvh_mute_time
   surface_wave_preprocessing  TimeLapseImaging._preprocessing_for_surface_waves (apis/timeLapseImaging.py:
                     51-71): bandpass + empty / noisy trace imputation + per-trace L2 norm
+  tracking_preprocessing  TimeLapseImaging._preprocess_for_tracking (apis/timeLapseImaging.py:74-102): median
+                    gate, empty-trace imputation, 0.08-1 Hz bandpass, 204/25 polyphase resampling onto the
+                    1 m x 50 Hz tracking grid, spatial bandpass (dvh_median_abs_gate, dvh_resample_rows_t,
+                    dvh_transpose_f64 with the kernels above)
 """
 from __future__ import annotations
 
@@ -191,3 +195,99 @@ def surface_wave_preprocessing(data, dt, method="surface_wave", flo=1.2, fhi=30,
     if return_indices:
         return out, tuple(int(i) for i in idx.cpu())
     return out
+
+
+_RESAMPLERS = {}
+
+
+def _resampler(up, down, dev):
+    """(up, down, half_len, h on the device) of scipy.signal.resample_poly(x, up, down)'s default filter, cached per
+    (up, down, device): the ratio reduced by its gcd, h = firwin(2 half_len + 1, 1 / max(up, down),
+    window=('kaiser', 5.0)) * up with half_len = 10 max(up, down); a 1 / 1 ratio is the identity (h = [1])."""
+    key = (int(up), int(down), str(dev))
+    if key not in _RESAMPLERS:
+        up, down = int(up), int(down)
+        if up < 1 or down < 1:
+            raise ValueError("up and down must be >= 1")
+        g = int(np.gcd(up, down))
+        up, down = up // g, down // g
+        if up == down == 1:
+            half_len, h = 0, np.ones(1)
+        else:
+            half_len = 10 * max(up, down)
+            h = scipy.signal.firwin(2 * half_len + 1, 1.0 / max(up, down), window=("kaiser", 5.0)) * up
+        _RESAMPLERS[key] = (up, down, half_len, torch.from_numpy(np.ascontiguousarray(h, dtype=np.float64)).to(dev))
+    return _RESAMPLERS[key]
+
+
+TRACKING_DX = 8.16  # channel spacing [m] of the record the tracking grid is resampled from (apis/timeLapseImaging.py:92)
+
+
+def tracking_preprocessing(data, dt, x0_channel, *, flo=0.08, fhi=1, flo_space=0.006, fhi_space=0.04, subsamp_factor=5,
+                           noise_level=10, channel0=400, up=204, down=25, return_info=False, _phases=None):
+    """TimeLapseImaging._preprocess_for_tracking (apis/timeLapseImaging.py:74-102) of a continuous record
+    [n_ch, n_t] with first channel number ``x0_channel`` -> (data_for_tracking [ceil(n_ch up / down),
+    ceil(n_t / subsamp_factor)] float64, dist_along_fiber_tracking, subsamp_factor): the tracking time axis is
+    ``t_axis[::subsamp_factor]``.  The input is left as is; a host array gives a host array, a device tensor a device
+    tensor (the distance axis is a host array either way, computed with the reference's expression).  On the device,
+    in the reference's order:
+      copy to float64 (a float32 record is promoted here; the reference keeps float32 up to resample_poly, whose
+        output is float64 -- the tracking grid is float64 throughout in this project)
+      means = median(|x|) per trace, traces with means > noise_level *= 0            dvh_median_abs_gate
+      find_noise_idx(30, empty_tr=True) / impute_noisy_trace                          dvh_trace_cleanup (flags 1)
+      bandpass_data(dt, flo, fhi)                                                     dvh_sosfiltfilt_planned
+      resample_poly(x[:, ::subsamp_factor], up, down), written transposed             dvh_resample_rows_t
+      bandpass_data_space(dist, flo_space, fhi_space) on the transposed rows (skipped when both are -1)
+      transpose back                                                                  dvh_transpose_f64
+    With return_info, also a dict: ``median`` per trace, the ``gated`` trace indices, the ``imputed`` trace index."""
+    on_device = isinstance(data, torch.Tensor) and data.is_cuda
+    if on_device:
+        t = data.to(torch.float64, copy=True).contiguous()
+    else:
+        host = np.asarray(data.detach().cpu() if isinstance(data, torch.Tensor) else data)
+        t = torch.from_numpy(np.array(host, dtype=np.float64, copy=True)).to(default_device())
+    if t.dim() != 2:
+        raise ValueError("data must be [n_ch, n_t]")
+    subsamp_factor = int(subsamp_factor)
+    if subsamp_factor < 1:
+        raise ValueError("subsamp_factor must be >= 1")
+    dev = t.device
+    n_ch, n_t = t.shape
+    up_r, down_r, half_len, h_t = _resampler(up, down, dev)
+    n_out = -(-n_ch * up_r // down_r)
+    n_t_out = -(-n_t // subsamp_factor)
+    space = not (flo_space == -1 and fhi_space == -1)
+    dist = np.arange(n_out) + (x0_channel - channel0) * TRACKING_DX
+    padlen = _design(dt, flo, fhi, dev)[1]  # 63 for every order-10 band-pass: the spatial filter's as well
+    if n_t <= padlen or (space and n_out <= padlen):
+        raise ValueError(f"The length of the input vector x must be greater than padlen, which is {padlen}.")
+    ev = (lambda k: _phases.setdefault(k, torch.cuda.Event(enable_timing=True)).record()) if _phases is not None \
+        else (lambda k: None)  # timing hook (tools/bench_tracking_prep.py)
+    st = _lib.stream_of(dev)
+    med = torch.empty(n_ch, dtype=torch.float64, device=dev)
+    gated = torch.empty(n_ch, dtype=torch.int32, device=dev)
+    stats = torch.empty(2 * n_ch, dtype=torch.float64, device=dev)
+    idx = torch.zeros(2, dtype=torch.int32, device=dev)
+    ev("start")
+    _lib.call("dvh_median_abs_gate", _lib.ptr(t), 1, n_ch, t.stride(0), n_t, float(noise_level), _lib.ptr(med),
+              _lib.ptr(gated), st)
+    ev("gate")
+    _lib.call("dvh_trace_cleanup", _lib.ptr(t), 1, n_ch, t.stride(0), n_t, 1, 30.0, _lib.ptr(stats), _lib.ptr(idx), st)
+    ev("cleanup")
+    bandpass_inplace(t, dt, flo, fhi)
+    ev("time_filter")
+    rs = torch.empty((n_t_out, n_out), dtype=torch.float64, device=dev)
+    _lib.call("dvh_resample_rows_t", _lib.ptr(t), 1, n_ch, t.stride(0), subsamp_factor, n_t_out, _lib.ptr(h_t),
+              half_len, up_r, down_r, _lib.ptr(rs), rs.stride(0), n_out, st)
+    ev("resample")
+    if space:
+        bandpass_inplace(rs, dist[1] - dist[0], flo_space, fhi_space)  # the axis' own step, as the reference takes it
+    ev("space_filter")
+    out = torch.empty((n_out, n_t_out), dtype=torch.float64, device=dev)
+    _lib.call("dvh_transpose_f64", _lib.ptr(rs), n_t_out, n_out, rs.stride(0), _lib.ptr(out), out.stride(0), st)
+    ev("transpose")
+    res = (out if on_device else out.cpu().numpy(), dist, subsamp_factor)
+    if return_info:
+        return res + (dict(median=med.cpu().numpy(), gated=np.flatnonzero(gated.cpu().numpy()),
+                           imputed=int(idx[0].cpu())),)
+    return res

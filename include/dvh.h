@@ -258,6 +258,35 @@ int dvh_cut_windows(const void* rec, int32_t in_dtype, int64_t n_rows, int64_t r
 /* SurfaceWaveWindow.mute_along_time (apis/data_classes.py:100-104). */
 int dvh_mute_time(void* data, int32_t dtype, int64_t n_rows, int32_t n_t, const double* taper, void* stream);
 
+/* ---------------------------------------------------------------- tracking-grid preprocessing
+ * TimeLapseImaging._preprocess_for_tracking (apis/timeLapseImaging.py:74-102): the median gate, then
+ * dvh_trace_cleanup (flags 1, threshold 30), dvh_sosfiltfilt_planned along time, the resampler below
+ * (fused with the [:, ::subsamp_factor] decimation, written transposed), dvh_sosfiltfilt_planned on the
+ * transposed rows (= along space, bandpass_data_space modules/utils.py:584-594) and the transpose back. */
+
+/* means = np.median(np.abs(x), axis=-1); x[means > noise_level] *= 0 (:76-77) on traces x[n_rows][n_t]
+ * (row_stride elements), in place.  The median is the exact order statistic (even n_t: (a + b) / 2 of the two
+ * middle values, in float64), any n_t >= 1; a trace holding a NaN has median NaN and is not gated; a gated
+ * trace is multiplied by 0 (-0.0 for negative samples, NaN for infinite ones, as numpy).  med_out (nullable):
+ * n_rows doubles; gated_out (nullable): n_rows int32, 1 where the trace was gated. */
+int dvh_median_abs_gate(void* x, int32_t dtype, int64_t n_rows, int64_t row_stride, int32_t n_t, double noise_level,
+                        double* med_out, int32_t* gated_out, void* stream);
+
+/* scipy.signal.resample_poly(x[:, ::t_step], up, down, axis=0).T of x[n_in][..] (row_stride elements, at least
+ * (n_t_out - 1) * t_step + 1 samples per row), float64 out[n_t_out][n_out] (out_stride doubles per row):
+ *   out[t][m] = sum_k h[half_len + down * m - up * k] * x[k][t * t_step],  0 <= k < n_in,
+ * over the k whose h index lies in [0, 2 * half_len]; h = the host-designed filter of 2 * half_len + 1 device
+ * doubles (resample_poly's default: firwin(2 * half_len + 1, 1 / max(up, down), window=('kaiser', 5.0)) * up with
+ * half_len = 10 * max(up, down), up / down reduced by their gcd).  n_out must be ceil(n_in * up / down) (-2
+ * otherwise, nothing launched).  Accumulates in float64. */
+int dvh_resample_rows_t(const void* x, int32_t dtype, int32_t n_in, int64_t row_stride, int32_t t_step,
+                        int32_t n_t_out, const double* h, int32_t half_len, int32_t up, int32_t down, double* out,
+                        int64_t out_stride, int32_t n_out, void* stream);
+
+/* dst[c][r] = src[r][c] for r < n_rows, c < n_cols (strides in doubles; src and dst must not overlap). */
+int dvh_transpose_f64(const double* src, int64_t n_rows, int64_t n_cols, int64_t src_stride, double* dst,
+                      int64_t dst_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
