@@ -1,17 +1,36 @@
 """ImagingWorkflowOneDirectory — the daily loop of apis/imaging_workflow.py:21-80 over the device classes.
 
-The reference reads a directory of records with ImagingIO (modules/imaging_IO.py) and tracks each record's vehicles
-with KF_tracking; both are outside the device hot path.  Here the records are any iterable of
+The reference reads a directory of records with ImagingIO (modules/imaging_IO.py), which is outside the device hot
+path, and tracks each record's vehicles with KF_tracking.  Here the records are any iterable of
 ``(data, x_axis, t_axis)`` -- what ImagingIO yields -- and the tracks come from ``tracks(k, imagingObj)``, a callable
 returning record k's tracking results ``(veh_states, dist_along_fiber_tracking, t_axis_tracking)`` (what
 track_cars / _preprocess_for_tracking leave on the object), or from a list of such tuples; ``imaging``'s start_x /
-end_x are the tracking span, as the reference passes them to track_cars.  The loop body is the reference's:
+end_x are the tracking span, as the reference passes them to track_cars.  ``DeviceTracker(start_x, end_x)`` is such a
+callable: it tracks every record on the device (TimeLapseImaging.track_vehicles), so that
+``ImagingWorkflowOneDirectory(records, tracks=DeviceTracker(start_x, end_x))`` runs the daily loop from raw records.  The loop body is the reference's:
 TimeLapseImaging -> select_surface_wave_windows -> get_images -> ``avg_image += images.avg_image`` (a sum of the
 per-record means, starting from 0), snapshots every ``n_min_save`` minutes, then ``save_avg_disp_to_npz``.
 """
 from __future__ import annotations
 
 from .timeLapseImaging import TimeLapseImaging
+
+
+class DeviceTracker:
+    """tracks(k, imagingObj) for ImagingWorkflowOneDirectory: the record's vehicles tracked on the device, as the
+    reference's loop does with track_cars(start_x, end_x, tracking_args, show_plot=False) (:55-56)."""
+
+    def __init__(self, start_x, end_x, tracking_args=None, reverse_amp=True, sigma_a=0.01):
+        self.start_x = start_x
+        self.end_x = end_x
+        self.tracking_args = tracking_args
+        self.reverse_amp = reverse_amp
+        self.sigma_a = sigma_a
+
+    def __call__(self, k, imagingObj):
+        veh_states = imagingObj.track_vehicles(self.start_x, self.end_x, self.tracking_args,
+                                               reverse_amp=self.reverse_amp, sigma_a=self.sigma_a)
+        return veh_states, imagingObj.dist_along_fiber_tracking, imagingObj.t_axis_tracking
 
 
 class ImagingWorkflowOneDirectory:

@@ -1,4 +1,4 @@
-"""TimeLapseImaging — apis/timeLapseImaging.py:22-211 on the device, without the tracker itself.
+"""TimeLapseImaging — apis/timeLapseImaging.py:22-211 on the device.
 
 Mirrors the reference class's constructor, attributes and imaging methods:
   _preprocessing_for_surface_waves  :50-71   bandpass + empty / noisy trace imputation + trace norm
@@ -13,18 +13,18 @@ Mirrors the reference class's constructor, attributes and imaging methods:
   get_images                        :198-201 DispersionImagesFromWindows (flavour B) or
                                              VirtualShotGathersFromWindows (xcorr) of sw_selector
   save_avg_disp_to_npz              :205-206
-The tracker (track_cars :106-120: find_peaks, the detection likelihood and the Kalman loop of KF_tracking,
-apis/tracking.py) is sequential host work outside the device hot path and stays external.
+  track_vehicles                    :104-119 track_cars without its plot: KF_tracking of this package
+                                             (apis/tracking.py: dvh_find_peaks_rows, dvh_peak_likelihood,
+                                             dvh_kf_track) on data_for_tracking, which stays on the device
 The constructor skips the tracking preprocessing (unlike the reference's); the flow from a raw record is
 
   obj = TimeLapseImaging(data, x_axis, t_axis)
-  obj.preprocess_for_tracking()                      # data_for_tracking, dist_along_fiber_tracking, t_axis_tracking
-  veh_states = <external tracker>(obj.data_for_tracking[start_idx:end_idx + 1:3], ...)
-  obj.set_veh_states(veh_states, start_x)            # tracks on the grid left by preprocess_for_tracking
+  obj.track_vehicles(start_x, end_x)                 # preprocess_for_tracking() if needed, then veh_states
   obj.select_surface_wave_windows(x0)
 
-Tracks made elsewhere, with their own grid (e.g. the reference's tracker run on the CPU, or stored tracks),
-are attached with ``set_tracking`` instead.
+``track_cars`` itself (whose default draws the detection plot) still raises.  Tracks made elsewhere are attached
+with ``set_veh_states`` (on the grid left by preprocess_for_tracking) or, with their own grid (e.g. the reference's
+tracker run on the CPU, or stored tracks), with ``set_tracking``.
 """
 from __future__ import annotations
 
@@ -33,6 +33,10 @@ import numpy as np
 from ..preprocess import surface_wave_preprocessing, tracking_preprocessing
 from .data_classes import SurfaceWaveSelector
 from .imaging_classes import DispersionImagesFromWindows, VirtualShotGathersFromWindows
+from .tracking import KF_tracking
+
+# apis/imaging_workflow.py:14-20
+DEFAULT_TRACKING_PARAM = {"detect": {"minprominence": 0.2, "minseparation": 50, "prominenceWindow": 600}}
 
 channel_prop = {"odh3": {"start_ch": 400, "dx": 8.16}}  # apis/timeLapseImaging.py:14-19
 
@@ -89,13 +93,30 @@ class TimeLapseImaging:
         self.start_x = start_x
         self.end_x = end_x
 
+    def track_vehicles(self, start_x, end_x, tracking_args=None, reverse_amp=True, sigma_a=0.01):
+        """track_cars (:104-119) without the plot: detection over the 15 rows from start_x (sigma = 0.08), then the
+        tracks of every third row up to end_x.  The grid stays on the device and is not negated: reverse_amp is the
+        sign the peak picking applies on load.  tracking_args=None takes DEFAULT_TRACKING_PARAM."""
+        if not hasattr(self, "data_for_tracking"):
+            self.preprocess_for_tracking()
+        self.start_x = start_x
+        self.end_x = end_x
+        self.tracking_args = tracking_args if tracking_args else DEFAULT_TRACKING_PARAM
+        self.tracking = KF_tracking(data=self.data_for_tracking, t_axis=self.t_axis_tracking,
+                                    x_axis=self.dist_along_fiber_tracking, args=self.tracking_args,
+                                    sign=-1 if reverse_amp else 1)
+        veh_base = self.tracking.detect_in_one_section(start_x=self.start_x, nx=15, sigma=0.08)
+        self.veh_states = self.tracking.tracking_with_veh_base(start_x=self.start_x, end_x=self.end_x,
+                                                               veh_base=veh_base, sigma_a=sigma_a)
+        return self.veh_states
+
     def track_cars(self, *args, **kwargs):
-        raise NotImplementedError("vehicle tracking (KF_tracking, apis/tracking.py) is outside the device hot path; "
-                                  "attach tracks with set_tracking()")
+        raise NotImplementedError("track_cars draws the detection plot; track_vehicles(start_x, end_x, tracking_args) "
+                                  "tracks on the device without it (or attach tracks with set_tracking())")
 
     def select_surface_wave_windows(self, x0, **kwargs):
         if not hasattr(self, "veh_states"):
-            raise AttributeError("no vehicle tracks: call set_tracking() first")
+            raise AttributeError("no vehicle tracks: call track_vehicles() or set_tracking() first")
         args = (self.distances_along_fiber, self.t_axis, x0, self.start_x, self.veh_states,
                 self.dist_along_fiber_tracking, self.t_axis_tracking)
         self.sw_selector = SurfaceWaveSelector(self.data_for_imaging, *args, **kwargs)

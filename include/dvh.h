@@ -287,6 +287,60 @@ int dvh_resample_rows_t(const void* x, int32_t dtype, int32_t n_in, int64_t row_
 int dvh_transpose_f64(const double* src, int64_t n_rows, int64_t n_cols, int64_t src_stride, double* dst,
                       int64_t dst_stride, void* stream);
 
+/* ---------------------------------------------------------------- vehicle tracking
+ * KF_tracking (apis/tracking.py:21-168) on the float64 tracking grid: peak picking per grid row, the detection
+ * curve of detect_in_one_section and the association / Kalman loop of tracking_with_veh_base.  The rejection of
+ * unrealistic tracks and the NaN interpolation work on the small result on the host. */
+
+/* Longest row dvh_find_peaks_rows takes (-4 above it, nothing launched).  Rows of up to 6 000 samples are staged
+ * in LDS, longer ones are read from global memory. */
+#define DVH_FIND_PEAKS_MAX_NT 16384
+
+/* scipy.signal.find_peaks(sign * x[r], distance=distance, prominence=min_prominence, wlen=wlen)[0] for the n_sel
+ * rows r = row0 + k * row_step of the row-major float64 matrix x (row_stride doubles per row, n_t >= 1 samples).
+ * sign is +1 or -1 and is applied on load (negation is exact).  SciPy's order and rules:
+ *   local maxima  a sample strictly above its left neighbour whose run of equal samples is followed by a strictly
+ *                 lower one is one peak at (left + right) / 2 (integer division); the first and last sample are
+ *                 never peaks and a run touching either end gives none; a comparison with NaN is false.
+ *   distance      (<= 0: off; else ceil(distance)) peaks are visited from the highest to the lowest, a peak that is
+ *                 still kept removes every peak closer than `distance` samples on both sides, a removed peak
+ *                 removes nothing; equal heights are visited larger index first.
+ *   prominence    (use_prominence == 0: off) of the peaks the distance rule kept: scans run outward from the peak
+ *                 while x[i] <= x[peak], inside [peak - wlen / 2, peak + wlen / 2] clipped to the row with
+ *                 wlen = ceil(wlen) (wlen <= 1, 0 or negative included: the whole row), tracking the minimum;
+ *                 prominence = x[peak] - max(left_min, right_min); kept when prominence >= min_prominence.
+ * peaks[n_sel][cap] receives the ascending sample indices and count[n_sel] their number; a row with more than cap
+ * peaks gets count = cap, its first cap peaks and status = 1 (status: nullable, n_sel int32, 0 otherwise); nothing
+ * is written past cap.  prominences (nullable): [n_sel][cap], the prominence of every stored peak (computed even
+ * when use_prominence is 0). */
+int dvh_find_peaks_rows(const double* x, int64_t row_stride, int32_t n_t, int64_t row0, int64_t row_step,
+                        int32_t n_sel, int32_t sign, double distance, int32_t use_prominence, double min_prominence,
+                        double wlen, int32_t* peaks, int32_t cap, int32_t* count, double* prominences,
+                        int32_t* status, void* stream);
+
+/* detect_in_one_section's curve (apis/tracking.py:30-42, likelihood_1d modules/car_tracking_utils.py:21-26):
+ *   out[t] = sum_r sum_p norm.pdf(t_axis[t], loc=t_axis[peaks[r][p]], scale=sigma),  r < n_rows, p < count[r],
+ * accumulated in the reference's order (a row's peaks first, then the rows); peaks / count as written by
+ * dvh_find_peaks_rows with the same cap; t_axis, out: n_t device doubles.  n_rows = 0 gives zeros.  The vehicle
+ * bases are then dvh_find_peaks_rows on out with the distance on and the prominence off (the reference's
+ * height = max * 0. holds for every sample of a non-negative sum). */
+int dvh_peak_likelihood(const int32_t* peaks, int32_t cap, const int32_t* count, int32_t n_rows,
+                        const double* t_axis, int32_t n_t, double sigma, double* out, void* stream);
+
+/* The association and Kalman loop of tracking_with_veh_base (apis/tracking.py:101-155), one thread per vehicle,
+ * over the peak lists of the n_steps tracked rows (peaks[n_steps][cap], count[n_steps], every row ascending as
+ * dvh_find_peaks_rows writes it: the match is found by bisection) at positions x_sel[n_steps] (device doubles).  veh_states[n_veh][n_steps] receives NaN or the matched peak index.  Per step and vehicle, as the
+ * reference has it:
+ *   search base  veh_base[v] while the vehicle has 0 or 1 matches; with exactly 1 the state is re-seeded every step
+ *                as [that match, 0] with P = 0 and Xv = that row's position; otherwise the predicted arrival
+ *                truncated toward zero, with delta_x = x_sel[k] - Xv, A = [[1, delta_x], [0, 1]] and
+ *                Q = sigma_a [[delta_x^4 / 4, delta_x^3 / 2], [delta_x^3 / 2, delta_x^2]].
+ *   match        the nearest peak with 0 < peak - base <= 30, else the nearest with -15 < peak - base <= 0, else NaN.
+ *   update       with R = 1, C = [1, 0], only once the vehicle has more than two matches and this step matched; Xv
+ *                moves only then. */
+int dvh_kf_track(const int32_t* peaks, int32_t cap, const int32_t* count, int32_t n_steps, const double* x_sel,
+                 const int32_t* veh_base, int32_t n_veh, double sigma_a, double* veh_states, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
