@@ -1,7 +1,7 @@
 // Wave-resident Stockham FFT for gfx950 (CDNA4, wave64).
 //
 // One 64-lane wave owns one complex transform of length N held in two LDS buffers (ping-pong);
-// stages are radix 2/3/4/5 with compile-time plans, so every loop bound and index stride folds.
+// stages are radix 2/3/4/5/10 with compile-time plans, so every loop bound and index stride folds.
 // Forward transform X[f] = sum_n x[n] exp(-2*pi*i*f*n/N); the inverse is obtained by the caller
 // through conj(FFT(conj(.))).  Twiddles exp(-2*pi*i*m/N) live in a block-shared LDS table.
 //
@@ -91,6 +91,23 @@ template <> struct Dft<5> {
   }
 };
 
+// 10-point DFT as Good-Thomas 2 x 5 (2 and 5 coprime: no internal twiddles), natural order in and out: input
+// n = (5 n1 + 2 n2) mod 10, output k = (5 k1 + 6 k2) mod 10, W10^(n k) = W2^(n1 k1) W5^(n2 k2).  Two independent
+// Dft<5> chains over n2, then five Dft<2> over n1; the permutations are compile-time register renames.
+template <> struct Dft<10> {
+  static __device__ __forceinline__ void run(float2 (&a)[10]) {
+    float2 e[5] = {a[0], a[2], a[4], a[6], a[8]};  // n1 = 0
+    float2 o[5] = {a[5], a[7], a[9], a[1], a[3]};  // n1 = 1
+    Dft<5>::run(e);
+    Dft<5>::run(o);
+#pragma unroll
+    for (int k2 = 0; k2 < 5; ++k2) {
+      a[(6 * k2) % 10] = cadd(e[k2], o[k2]);
+      a[(6 * k2 + 5) % 10] = csub(e[k2], o[k2]);
+    }
+  }
+};
+
 // 16-point DFT in registers, natural order in and out (4 x 4: radix-4 DFTs over t2 of a[t1 + 4 t2], twiddles
 // W16^(t1 q2), radix-4 DFTs over t1 into a[q2 + 4 q1]).  HALF: only a[0..7] are non-zero (a zero-padded input).
 template <bool HALF = false>
@@ -148,9 +165,26 @@ __device__ __forceinline__ void twiddle16(float2 (&a)[16], float2 w1, float2 w4,
   }
 }
 
-template <int N, int Ls, int R>
-__device__ __forceinline__ void stockham_stage(const float2* __restrict__ in, float2* __restrict__ out,
-                                               const float2* __restrict__ tw, int lane) {
+// a[t] *= w^t, t = 1..9, from w^1 and w^5 (table reads: every power within three roundings of the table's)
+__device__ __forceinline__ void twiddle10(float2 (&a)[10], float2 w1, float2 w5) {
+  const float2 w2 = cmul(w1, w1), w3 = cmul(w2, w1), w4 = cmul(w5, make_float2(w1.x, -w1.y));
+  a[1] = cmul(a[1], w1);
+  a[2] = cmul(a[2], w2);
+  a[3] = cmul(a[3], w3);
+  a[4] = cmul(a[4], w4);
+  a[5] = cmul(a[5], w5);
+  a[6] = cmul(a[6], cmul(w5, w1));
+  a[7] = cmul(a[7], cmul(w5, w2));
+  a[8] = cmul(a[8], cmul(w5, w3));
+  a[9] = cmul(a[9], cmul(w5, w4));
+}
+
+// One stage.  IP / OP pad the buffers against bank conflicts: the input holds IP unused entries after every N / R
+// (index i + t N / R becomes i + t (N / R + IP)), the output OP after every Ls R (the butterfly's block (i - k) R
+// becomes (i / Ls)(Ls R + OP)).  Every lane reads all its inputs before its first store and a wave runs in lockstep,
+// so `out` may overlap entries of `in`; the __restrict__ wrapper below is for buffers that do not.
+template <int N, int Ls, int R, int IP = 0, int OP = 0>
+__device__ __forceinline__ void stockham_stage_any(const float2* in, float2* out, const float2* tw, int lane) {
   constexpr int NB = N / R;
   constexpr int TWS = N / (Ls * R);
   static_assert(N % (Ls * R) == 0, "plan does not divide N");
@@ -160,8 +194,12 @@ __device__ __forceinline__ void stockham_stage(const float2* __restrict__ in, fl
       const int k = i % Ls;
       float2 a[R];
 #pragma unroll
-      for (int t = 0; t < R; ++t) a[t] = lds_ld(in, i + t * NB);
-      if (Ls > 1) {
+      for (int t = 0; t < R; ++t) a[t] = lds_ld(in, i + t * (NB + IP));
+      if constexpr (Ls > 1 && R == 10) {
+        // two table reads per butterfly (k TWS and 5 k TWS <= N / 2), the other powers from those (one read per
+        // power measured no faster: DESIGN.md)
+        twiddle10(a, tw[k * TWS], tw[5 * k * TWS]);
+      } else if constexpr (Ls > 1) {
         // one table read per butterfly, powers by recurrence (LDS reads are the scarcer resource; per-power table
         // reads measured 8 % slower)
         const float2 w1 = tw[k * TWS];
@@ -173,9 +211,17 @@ __device__ __forceinline__ void stockham_stage(const float2* __restrict__ in, fl
         }
       }
       Dft<R>::run(a);
-      const int base = (i - k) * R + k;
+      if constexpr (Ls == 1 && R == 10 && OP == 0) {
+        // out[10 i + q]: five 16-byte stores at an 80-byte lane stride, which tile the 32 banks within each 8-lane
+        // store group (the buffers are 16-byte aligned)
+        float4* d = reinterpret_cast<float4*>(out + R * i);
 #pragma unroll
-      for (int q = 0; q < R; ++q) out[base + q * Ls] = a[q];
+        for (int q = 0; q < R; q += 2) d[q >> 1] = make_float4(a[q].x, a[q].y, a[q + 1].x, a[q + 1].y);
+      } else {
+        const int base = OP == 0 ? (i - k) * R + k : (i / Ls) * (Ls * R + OP) + k;
+#pragma unroll
+        for (int q = 0; q < R; ++q) out[base + q * Ls] = a[q];
+      }
     }
   };
   // Short radix <= 5 stages (<= 2 rounds of 64 butterflies) are unrolled so that the second round's LDS reads
@@ -184,10 +230,18 @@ __device__ __forceinline__ void stockham_stage(const float2* __restrict__ in, fl
   if constexpr (NB <= 128 && R <= 5) {
 #pragma unroll
     for (int i0 = 0; i0 < NB; i0 += 64) round(i0);
+  } else if constexpr (NB <= 64) {
+    round(0);
   } else {
 #pragma unroll 1
     for (int i0 = 0; i0 < NB; i0 += 64) round(i0);
   }
+}
+
+template <int N, int Ls, int R>
+__device__ __forceinline__ void stockham_stage(const float2* __restrict__ in, float2* __restrict__ out,
+                                               const float2* __restrict__ tw, int lane) {
+  stockham_stage_any<N, Ls, R>(in, out, tw, lane);
 }
 
 template <int N, int Ls, int... Rs> struct Stockham;
@@ -209,7 +263,7 @@ template <int N, int Ls, int R, int... Rs> struct Stockham<N, Ls, R, Rs...> {
 // zero-padded linear correlation (N >= 2w - 1) and folded back to the circular one in the epilogue.
 template <int N> struct FftPlan;
 template <> struct FftPlan<250> { using T = Stockham<250, 1, 2, 5, 5, 5>; };
-template <> struct FftPlan<500> { using T = Stockham<500, 1, 4, 5, 5, 5>; };
+template <> struct FftPlan<500> { using T = Stockham<500, 1, 10, 10, 5>; };
 template <> struct FftPlan<1000> { using T = Stockham<1000, 1, 4, 2, 5, 5, 5>; };
 template <> struct FftPlan<512> { using T = Stockham<512, 1, 4, 4, 4, 4, 2>; };
 template <> struct FftPlan<1024> { using T = Stockham<1024, 1, 4, 4, 4, 4, 4>; };

@@ -16,7 +16,7 @@
 //                        loads staged in registers one sub-window ahead.  PAD: N >= 2w - 1 zero padded,
 //                        linear correlation folded back to circular in c().
 //   EngF500              N = w = 500 (wlen = 2 s at 250 Hz, the reference's operating point): the
-//                        4 x 5 x 5 x 5 Stockham transform with its first and last stages in registers.
+//                        10 x 10 x 5 Stockham transform with its first and last stages in registers.
 //   EngP1024             w <= 512 without an exact engine (w = 499): zero-padded 4^5 transform, first and
 //                        last stages in registers, as EngF500 (pivot-slice table, cross-pass packing).
 // (Engine variants measured and not kept are listed in DESIGN.md.)
@@ -303,9 +303,9 @@ __device__ __forceinline__ const int32_t* tab_head(const float2* tab, int n_pass
 
 // ------------------------------------------------------------------------------------------------
 // FusedOps<E>: the row-task logic of the engines whose first and last transform stages run in registers
-// (EngF500, EngP1024).  E provides the transform: N / NFFT, NJ (sample registers), NH (half-spectrum slots
-// per lane), kTabBins, bin(l, j), load_ri() (a sub-window's samples into registers), stage1() (registers ->
-// LDS), finish_with(acc) (the remaining stages, then acc(j, Z[f], Z[N - f]) for every half-spectrum slot j
+// (EngF500, EngP1024).  E provides the transform: N / NFFT, kNJ (sample registers per lane; not E::NJ, the
+// lags per lane of the epilogues in dvh_vsg.hip), NH (half-spectrum slots per lane), kTabBins, bin(l, j),
+// load_ri() (a sub-window's samples into registers), stage1() (registers -> LDS), finish_with(acc) (the remaining stages, then acc(j, Z[f], Z[N - f]) for every half-spectrum slot j
 // of the lane), inverse() and c() (the correlation at lag k after the inverse).  FusedOps holds the per-wave
 // state and the three ways a row task forms its accumulated cross spectra:
 //   spectra():     one complex transform per sub-window, z = pivot + i receiver;
@@ -701,19 +701,28 @@ struct FusedOps {
 };
 
 // ------------------------------------------------------------------------------------------------
-// EngF500: N = w = 500 Stockham (4 x 5 x 5 x 5) with the first and last stages fused into registers.
-//   stage 1 (radix 4, span 1) reads its inputs straight from the prefetched sub-window samples
-//     (lane i < 125 of round r holds samples i + 125 t) -- no LDS store of the raw window;
-//   stages 2-3 go through LDS (one twiddle read per butterfly, powers by recurrence);
-//   stage 4 (radix 5, span 100) runs butterflies k and 100 - k in the same lane (l <= 50), so the
+// EngF500: N = w = 500 Stockham (10 x 10 x 5) with the first and last stages fused into registers.
+//   stage 1 (radix 10, span 1) reads its inputs straight from the prefetched sub-window samples (lane i < 50
+//     holds samples i + 50 t, t < 10, of both slices) -- no LDS store of the raw window; one Good-Thomas 2 x 5
+//     butterfly per lane, its outputs X[10 i .. 10 i + 9] stored as five 16-byte pieces (buffer B);
+//   stage 2 (radix 10, span 10: 50 butterflies, one round) goes through LDS, two twiddle reads per butterfly
+//     (w, w^5), into buffer A padded by kPad entries after every 100, which makes its 8-byte stores conflict free
+//     (unpadded, the lanes of a 16-lane store group that straddle i / 10 land 800 B apart: 25 of 32 banks shared);
+//   stage 3 (radix 5, span 100) runs butterflies k and 100 - k in the same lane (l <= 50), so the
 //     lane holds X[k + 100 q] and its Hermitian partners X[N - f] and forms the cross spectra of its
 //     five bins in registers -- no LDS write of the spectrum and no partner reads.
+// Per forward transform: 2 LDS round trips and 3 wave barriers, 5 ds_write_b128 + 10 ds_write_b64, 10 + 2 LDS reads
+// in the middle stage, one round of 64 lanes per stage (4 x 5 x 5 x 5, the previous plan: 3 round trips, 4
+// barriers, 4 + 20 stores, 20 + 4 reads, 2 / 2 + 2 rounds; DESIGN.md has both measured).
+// The padded buffer A is 4 kPad entries longer than the 500 of buffer B behind it and overlaps B's first entries:
+// the middle stage has read all of B before its first store, and B is rewritten only by the next stage 1.
 // Half-spectrum slots per lane l: j < 3 -> f = l + 100 j (l <= 50); j = 3, 4 -> f = 100 - l + 100 (j - 3)
 // (1 <= l <= 49): each of the 251 bins f <= 250 exactly once.
-struct EngF500 : FusedOps<EngF500, 8, 5> {
+struct EngF500 : FusedOps<EngF500, 10, 5> {
   static constexpr int N = 500;
   static constexpr int NFFT = 500;
-  static constexpr int NJ = 8;
+  static constexpr int NJ = 8;   // lags per lane in the epilogues (dvh_vsg.hip)
+  static constexpr int kNZ = 10;  // sample registers per lane: samples i + 50 t
   static constexpr int NH = 5;
   static constexpr int kWaves = 4;
   static constexpr bool kNextTask = false;
@@ -721,8 +730,9 @@ struct EngF500 : FusedOps<EngF500, 8, 5> {
   static constexpr size_t kBlockBytes = sizeof(float2) * N;     // twiddle table
   static constexpr size_t kWaveBytes = sizeof(float2) * 2 * N;  // ping-pong buffers
   static constexpr int kBufA = N;                               // bufB = bufA + kBufA
+  static constexpr int kPad = 6;  // 2 (100 + kPad) = 20 mod 32 dwords: the 20-dword runs of consecutive i / 10 abut
 
-  __device__ EngF500(char* lds, int wave, int lane_) : FusedOps<EngF500, 8, 5>(lds, wave, lane_, N) {}
+  __device__ EngF500(char* lds, int wave, int lane_) : FusedOps<EngF500, kNZ, 5>(lds, wave, lane_, N) {}
   static __device__ void block_init(char* lds) { init_twiddles<N>(reinterpret_cast<float2*>(lds)); }
 
   static __device__ __forceinline__ int bin(int l, int j) {
@@ -731,57 +741,48 @@ struct EngF500 : FusedOps<EngF500, 8, 5> {
   }
   static __device__ __forceinline__ int slot(int n) { return n; }
 
-  // stage-1 operands z[4 r + t] = (re, im)[i + 125 t], i = lane + 64 r, of the slices starting at re / im
-  // Branch-free: lanes past the 125 stage-1 butterflies (round 1, lane >= 61) load lane 60's samples
-  // again, which stage1() does not store and which leave the non-zero tests unchanged; with im ==
-  // nullptr the receiver is loaded into both halves (the second half's result is discarded).
-  __device__ __forceinline__ void load_ri(const float* re, const float* im, float2 (&z)[8]) const {
+  // stage-1 operands z[t] = (re, im)[i + 50 t], t < 10, i = min(lane, 49), of the slices starting at re / im.
+  // Branch-free: lanes past the 50 stage-1 butterflies load lane 49's samples again, which stage1() does not
+  // store and which leave the non-zero tests unchanged; with im == nullptr the receiver is loaded into both
+  // halves (the second half's result is discarded).
+  __device__ __forceinline__ void load_ri(const float* re, const float* im, float2 (&z)[kNZ]) const {
     const float* ip = im ? im : re;
+    const int i = min(lane, 49);
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int i = r == 0 ? lane : min(lane + 64, 124);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int n = i + 125 * u;
-        z[4 * r + u] = make_float2(re[n], ip[n]);
-      }
+    for (int t = 0; t < kNZ; ++t) {
+      const int n = i + 50 * t;
+      z[t] = make_float2(re[n], ip[n]);
     }
   }
 
-  __device__ __forceinline__ void stage1(const float2 (&z)[8]) const {
+  __device__ __forceinline__ void stage1(const float2 (&z)[kNZ]) const {
+    const int i = opaque(lane);
+    if (i < 50) {
+      float2 a[10];
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int i = lane + 64 * r;
-      if (r == 0 || i < 125) {
-        float2 a[4] = {z[4 * r], z[4 * r + 1], z[4 * r + 2], z[4 * r + 3]};
-        Dft<4>::run(a);
-        // the four outputs are two 16-byte stores, X[4i..4i+1] and X[4i+2..4i+3]; with both in that order an
-        // 8-lane store group hits banks 8i mod 32 twice (2-way conflict, the engine's only one).  Lanes with
-        // i & 4 store their second pair first, so each store's eight 16-byte pieces tile the 32 banks.
-        const bool sw = (lane & 4) != 0;
-        const int o = sw ? 2 : 0;
-        float4* d = reinterpret_cast<float4*>(bufB + 4 * i);
-        d[o >> 1] = sw ? make_float4(a[2].x, a[2].y, a[3].x, a[3].y) : make_float4(a[0].x, a[0].y, a[1].x, a[1].y);
-        d[(2 - o) >> 1] = sw ? make_float4(a[0].x, a[0].y, a[1].x, a[1].y) : make_float4(a[2].x, a[2].y, a[3].x, a[3].y);
-      }
+      for (int t = 0; t < 10; ++t) a[t] = z[t];
+      Dft<10>::run(a);
+      // X[10 i .. 10 i + 9] as five 16-byte stores: the 80-byte lane stride tiles the 32 banks within each
+      // 8-lane store group (20 i mod 32 = 0, 20, 8, 28, 16, 4, 24, 12), no swizzle needed
+      float4* d = reinterpret_cast<float4*>(bufB + 10 * i);
+#pragma unroll
+      for (int q = 0; q < 10; q += 2) d[q >> 1] = make_float4(a[q].x, a[q].y, a[q + 1].x, a[q + 1].y);
     }
   }
 
-  // stages 2-4 of the transform whose stage-1 output is in bufB; for every half-spectrum slot j of
+  // stages 2-3 of the transform whose stage-1 output is in bufB; for every half-spectrum slot j of
   // the lane (compile-time j, valid slots only), acc(j, Z[f], Z[N - f]) with f = bin(lane, j)
   template <class F>
   __device__ __forceinline__ void finish_with(F&& acc) const {
     wave_sync();
-    stockham_stage<N, 4, 5>(bufB, bufA, tw, lane);
-    wave_sync();
-    stockham_stage<N, 20, 5>(bufA, bufB, tw, lane);
+    stockham_stage_any<N, 10, 10, 0, kPad>(bufB, bufA, tw, opaque(lane));
     wave_sync();
     const int ln = opaque(lane);  // the stage's addresses formed per call, not held in registers between calls
     if (ln <= 50) {
       float2 XA[5], XB[5];
       const bool pair = ln >= 1 && ln <= 49;
-      last_bfly_from(bufB, ln, XA);
-      if (pair) last_bfly_from(bufB, 100 - ln, XB);
+      last_bfly_from(bufA, ln, XA);
+      if (pair) last_bfly_from(bufA, 100 - ln, XB);
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         // partner X[N - f] of f = l + 100 j is X[(100 - l) + 100 (4 - j)]
@@ -799,10 +800,10 @@ struct EngF500 : FusedOps<EngF500, 8, 5> {
     wave_sync();
   }
 
-  // radix-5 butterfly k of the last stage (span 100): X[k + 100 q], q < 5
+  // radix-5 butterfly k of the last stage (span 100): X[k + 100 q], q < 5, from the padded buffer
   __device__ __forceinline__ void last_bfly_from(const float2* src, int k, float2 (&x)[5]) const {
 #pragma unroll
-    for (int t = 0; t < 5; ++t) x[t] = lds_ld(src, k + 100 * t);
+    for (int t = 0; t < 5; ++t) x[t] = lds_ld(src, k + (100 + kPad) * t);
     const float2 w1 = tw[k];
     float2 wt = w1;
 #pragma unroll
@@ -814,9 +815,20 @@ struct EngF500 : FusedOps<EngF500, 8, 5> {
   }
 
   __device__ const float2* inverse(const float2 (&Cf)[NH], const float2 (&Co)[NH]) {
-    store_conj_hermitian<EngF500>(bufA, Cf, Co, lane);
+    // 10 x 10 x 5 as the forward transform: B -> A -> padded B -> A.  The padded buffer starts 4 kPad entries
+    // before B, over the end of A: the middle stage has read all of A before its first store, and the last stage
+    // writes those entries of A (X[476..499], its second round) after its first round has read the overlapped
+    // inputs (padded entries < 24).
+    float2* const bufP = bufB - 4 * kPad;
+    store_conj_hermitian<EngF500>(bufB, Cf, Co, lane);
     wave_sync();
-    return FftPlan<N>::T::run(bufA, bufB, tw, lane);
+    stockham_stage_any<N, 1, 10>(bufB, bufA, tw, opaque(lane));
+    wave_sync();
+    stockham_stage_any<N, 10, 10, 0, kPad>(bufA, bufP, tw, opaque(lane));
+    wave_sync();
+    stockham_stage_any<N, 100, 5, kPad, 0>(bufP, bufA, tw, opaque(lane));
+    wave_sync();
+    return bufA;
   }
 
   __device__ const float2* correlate(const RowTask& t, const RowTask& nt, bool has_next, int w, int hop) {
@@ -916,7 +928,6 @@ struct EngP1024 : FusedOps<EngP1024, 8, 9> {
 
   // the four outputs of radix-4 butterfly i of a span-1 stage (out[4 i + q]) as two 16-byte stores at a 32-byte
   // lane stride; lanes with i & 4 store their second pair first so that every 8-lane store group tiles the 32 banks
-  // (as EngF500's stage 1)
   static __device__ __forceinline__ void store4(float2* out, int i, float2 x0, float2 x1, float2 x2, float2 x3) {
     const bool sw = (i & 4) != 0;
     const int o = sw ? 2 : 0;
