@@ -1,7 +1,9 @@
 """ImagingWorkflowOneDirectory — the daily loop of apis/imaging_workflow.py:21-80 over the device classes.
 
-The reference reads a directory of records with ImagingIO (modules/imaging_IO.py), which is outside the device hot
-path, and tracks each record's vehicles with KF_tracking.  Here the records are any iterable of
+Two constructor forms.  The reference's, ``(directory, root, tracking_args=None, method='surface_wave',
+imaging_IO_dict={})``: the records are read with this package's ImagingIO (modules/imaging_IO.py: the file and the
+index arithmetic on the host, savgol_filter(21, 15) and the scale on the device) and every record's vehicles are tracked
+on the device, as the reference tracks them with track_cars.  The records form: the records are any iterable of
 ``(data, x_axis, t_axis)`` -- what ImagingIO yields -- and the tracks come from ``tracks(k, imagingObj)``, a callable
 returning record k's tracking results ``(veh_states, dist_along_fiber_tracking, t_axis_tracking)`` (what
 track_cars / _preprocess_for_tracking leave on the object), or from a list of such tuples; ``imaging``'s start_x /
@@ -12,6 +14,8 @@ TimeLapseImaging -> select_surface_wave_windows -> get_images -> ``avg_image += 
 per-record means, starting from 0), snapshots every ``n_min_save`` minutes, then ``save_avg_disp_to_npz``.
 """
 from __future__ import annotations
+
+import os
 
 from .timeLapseImaging import TimeLapseImaging
 
@@ -34,18 +38,50 @@ class DeviceTracker:
 
 
 class ImagingWorkflowOneDirectory:
-    def __init__(self, records, tracks, method="surface_wave", time_interval=60.0, directory=None):
-        """records: iterable of (data, x_axis, t_axis); tracks: callable (k, imagingObj) -> (veh_states,
-        dist_along_fiber_tracking, t_axis_tracking), or a sequence of them; time_interval: seconds per record
-        (ImagingIO.get_time_interval)."""
+    def __init__(self, *args, **kwargs):
+        """Two forms.
+        (records, tracks, method='surface_wave', time_interval=60.0, directory=None) -- records: iterable of
+        (data, x_axis, t_axis); tracks: callable (k, imagingObj) -> (veh_states, dist_along_fiber_tracking,
+        t_axis_tracking), or a sequence of them; time_interval: seconds per record (ImagingIO.get_time_interval).
+        (directory, root, tracking_args=None, method='surface_wave', imaging_IO_dict={}) -- the reference's
+        constructor (apis/imaging_workflow.py:24-30), taken when the first argument is a path string and ``root`` is
+        given, as the second positional argument or by keyword: the records are ImagingIO(directory, root,
+        **imaging_IO_dict), smoothed and scaled on the device, and ``imaging`` tracks every record with
+        DeviceTracker(start_x, end_x, tracking_args) unless the extra keyword ``tracks=`` supplies the tracks."""
+        first = args[0] if args else kwargs.get("directory", kwargs.get("records"))
+        if isinstance(first, (str, os.PathLike)) and (len(args) >= 2 or "root" in kwargs) and "records" not in kwargs:
+            self._init_directory(*args, **kwargs)
+        else:
+            self._init_records(*args, **kwargs)
+
+    def _init_records(self, records, tracks, method="surface_wave", time_interval=60.0, directory=None):
         self.records = records
         self.tracks = tracks
         self.method = method
         self.time_interval = time_interval
         self.directory = directory
 
-    def _tracks_of(self, k, obj):
-        return self.tracks(k, obj) if callable(self.tracks) else self.tracks[k]
+    def _init_directory(self, directory, root, tracking_args=None, method="surface_wave", imaging_IO_dict=None, *,
+                        tracks=None):
+        from ..modules.imaging_IO import ImagingIO
+        self.directory = directory
+        self.root = root
+        self.imagingIO = ImagingIO(directory, root, **(imaging_IO_dict or {}))
+        self.time_interval = self.imagingIO.get_time_interval()
+        self.tracking_args = tracking_args
+        self.method = method
+        self.records = self.imagingIO
+        self.tracks = tracks
+
+    @staticmethod
+    def _tracks_of(tracks, k, obj):
+        return tracks(k, obj) if callable(tracks) else tracks[k]
+
+    def _tracker(self, start_x, end_x):
+        """The reference form without tracks=: track_cars(start_x, end_x, self.tracking_args) per record (:55-56)."""
+        if self.tracks is None and hasattr(self, "imagingIO"):
+            return DeviceTracker(start_x, end_x, self.tracking_args)
+        return self.tracks
 
     def imaging(self, start_x, end_x, x0, wlen_sw=8, length_sw=300, spatial_ratio=0.75, n_min_save=30,
                 temporal_spacing=None, num_to_stop=None, verbal=True, surface_wave_preprecessing_dict=None,
@@ -57,6 +93,7 @@ class ImagingWorkflowOneDirectory:
             raise TypeError("imaging_kwargs is required (the reference's get_images(**None) raises)")
         avg_image = 0
         num_veh = 0
+        tracks = self._tracker(start_x, end_x)
         self.avg_images_to_save = []
         n_win_save = int(n_min_save * 60 / self.time_interval)
         for k, (data, x_axis, t_axis) in enumerate(self.records):
@@ -66,7 +103,7 @@ class ImagingWorkflowOneDirectory:
                 print(f"working on window {k}, method={self.method}")
             obj = TimeLapseImaging(data, x_axis, t_axis, method=self.method,
                                    surface_wave_preprecessing_dict=surface_wave_preprecessing_dict)
-            veh_states, dist_trk, t_trk = self._tracks_of(k, obj)
+            veh_states, dist_trk, t_trk = self._tracks_of(tracks, k, obj)
             obj.set_tracking(veh_states, start_x, dist_trk, t_trk, end_x=end_x)
             obj.select_surface_wave_windows(x0=x0, wlen_sw=wlen_sw, length_sw=length_sw, spatial_ratio=spatial_ratio,
                                             temporal_spacing=temporal_spacing)

@@ -6,6 +6,8 @@
   bandpass_data modules/utils.py:179-189  -> dvh_sosfiltfilt (zero-phase order-10 Butterworth)
   extract_ridge_ref_idx modules/utils.py:621-678 -> dvh_ridge (one wave per ridge)
   disp_curve_stats  the statistics of plot_disp_curves (:680-713), without the figure
+  _cut_taper, _read_das_npz modules/utils.py:87-113 (host: the record file, its channel and taper cut; ImagingIO of
+                modules/imaging_IO.py smooths and scales the result on the device)
 Host arrays in, host arrays out, like the reference; device tensors are accepted too.
 """
 from __future__ import annotations
@@ -28,6 +30,39 @@ def _as_device_batch(data, device=None):
     if t.dim() == 2:
         t = t.unsqueeze(0)
     return t.contiguous() if t.stride(-1) != 1 else t
+
+
+def _first_at_or_above(axis, value):
+    """Index of the first axis entry >= value (0 when there is none, as np.argmax of an all-False mask)."""
+    return int(np.argmax(np.asarray(axis) >= value))
+
+
+def _cut_taper(data, t_axis):
+    """Trim the acquisition taper (modules/utils.py:87-92 of the reference): the sample whose time is nearest 0 sits
+    ``m`` samples into the record, and ``m`` samples leave at both ends of the data and of the time axis."""
+    m = int(np.argmin(np.abs(t_axis)))
+    keep = slice(m, data.shape[-1] - m)
+    return data[:, keep], t_axis[keep]
+
+
+def _read_das_npz(fname, **kwargs):
+    """One record file (keys data [n_ch, n_t], x_axis, t_axis) -> (data, x_axis, t_axis) cut as the reference's
+    reader cuts it (modules/utils.py:94-113).  Host work only: file reading and index arithmetic.
+      ch1, ch2    channel numbers; rows from the first x_axis >= ch1 up to, not including, the first x_axis >= ch2
+                  (defaults: the axis' first and last entry, so the last channel is dropped)
+      cut_taper   (default True) apply _cut_taper
+    A file that cannot be opened raises Exception("fname: <path>")."""
+    try:
+        npz = np.load(fname)
+    except Exception:
+        raise Exception(f"fname: {fname}")
+    x_axis, t_axis = npz["x_axis"], npz["t_axis"]
+    rows = slice(_first_at_or_above(x_axis, kwargs.get("ch1", x_axis[0])),
+                 _first_at_or_above(x_axis, kwargs.get("ch2", x_axis[-1])))
+    data = npz["data"][rows]
+    if kwargs.get("cut_taper", True):
+        data, t_axis = _cut_taper(data, t_axis)
+    return data, x_axis[rows], t_axis
 
 
 _PLANS = {}

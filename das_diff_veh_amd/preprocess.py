@@ -13,6 +13,9 @@
                     gate, empty-trace imputation, 0.08-1 Hz bandpass, 204/25 polyphase resampling onto the
                     1 m x 50 Hz tracking grid, spatial bandpass (dvh_median_abs_gate, dvh_resample_rows_t,
                     dvh_transpose_f64 with the kernels above)
+  savgol_smooth     ImagingIO.__getitem__'s savgol_filter(data, 21, 15) and ``data /= scale`` (modules/imaging_IO.py:
+                    44-46) in one pass: SciPy's mode='interp' filter as three host-designed linear maps
+                    (savgol_interp_operator), evaluated by dvh_savgol_rows
 """
 from __future__ import annotations
 
@@ -291,3 +294,71 @@ def tracking_preprocessing(data, dt, x0_channel, *, flo=0.08, fhi=1, flo_space=0
         return res + (dict(median=med.cpu().numpy(), gated=np.flatnonzero(gated.cpu().numpy()),
                            imputed=int(idx[0].cpu())),)
     return res
+
+
+_SAVGOL_OPS = {}
+_SAVGOL_DEV = {}
+
+
+def savgol_interp_operator(window_length, polyorder):
+    """scipy.signal.savgol_filter(x, window_length, polyorder) (mode='interp', along the last axis) as three linear
+    maps (h, el, er), cached per design: ``h = savgol_coeffs(W, P)[::-1]`` for the interior
+    (y[t] = sum_j h[j] x[t - half + j]) and the first / last ``half`` rows of the W x W matrix that savgol_filter
+    itself makes of the identity, one column at a time: el maps the first W samples onto the first half outputs, er
+    the last W onto the last half.  SciPy is the coefficient designer: at (21, 15) its taps are not the exact
+    least-squares ones (its Vandermonde solve is ill-conditioned; they are not even symmetric), and the reference's
+    output is defined by them."""
+    W, P = int(window_length), int(polyorder)
+    key = (W, P)
+    if key not in _SAVGOL_OPS:
+        if W % 2 == 0 or W < 3:
+            raise ValueError("window_length must be odd and >= 3")
+        if P >= W:
+            raise ValueError("polyorder must be less than window_length.")
+        half = W // 2
+        h = np.ascontiguousarray(scipy.signal.savgol_coeffs(W, P)[::-1], dtype=np.float64)
+        eye = np.eye(W)
+        m = np.stack([scipy.signal.savgol_filter(eye[:, c], W, P) for c in range(W)], axis=1)
+        _SAVGOL_OPS[key] = (h, np.ascontiguousarray(m[:half]), np.ascontiguousarray(m[W - half:]))
+    return _SAVGOL_OPS[key]
+
+
+def _savgol_device(window_length, polyorder, dev):
+    key = (int(window_length), int(polyorder), str(dev))
+    if key not in _SAVGOL_DEV:
+        _SAVGOL_DEV[key] = tuple(torch.from_numpy(a).to(dev) for a in savgol_interp_operator(window_length, polyorder))
+    return _SAVGOL_DEV[key]
+
+
+def savgol_smooth(data, window_length=21, polyorder=15, divisor=1.0):
+    """savgol_filter(data, window_length, polyorder) along time followed by ``/= divisor``: what
+    ImagingIO.__getitem__ (modules/imaging_IO.py:44-46) does to a record, in one pass of dvh_savgol_rows.  A host
+    array gives a host array, a device tensor a new device tensor (the input is left as is).  float32 and float64
+    are kept (float32: float64 sums rounded once, then divided in float32, as SciPy and numpy do); any other dtype
+    is converted to float64 on the host first, as SciPy does."""
+    on_device = isinstance(data, torch.Tensor) and data.is_cuda
+    if on_device:
+        if data.dtype not in (torch.float32, torch.float64):
+            raise TypeError("a device record must be float32 or float64")
+        shape = tuple(data.shape)
+    else:
+        host = np.asarray(data.detach().cpu() if isinstance(data, torch.Tensor) else data)
+        if host.dtype not in (np.float32, np.float64):
+            host = host.astype(np.float64)
+        shape = host.shape
+    if len(shape) < 1 or shape[-1] < int(window_length):
+        raise ValueError("If mode is 'interp', window_length must be less than or equal to the size of x.")
+    t = data if on_device else torch.from_numpy(np.ascontiguousarray(host)).to(default_device())
+    n_t = shape[-1]
+    rows = t.reshape(-1, n_t)
+    if rows.stride(-1) != 1 or (rows.shape[0] > 1 and rows.stride(0) < n_t):  # e.g. an expanded row dimension
+        rows = rows.contiguous()
+    dev = rows.device
+    h_t, el_t, er_t = _savgol_device(window_length, polyorder, dev)
+    out = torch.empty((rows.shape[0], n_t), dtype=rows.dtype, device=dev)
+    if rows.shape[0]:
+        _lib.call("dvh_savgol_rows", _lib.ptr(rows), 0 if rows.dtype == torch.float32 else 1, rows.shape[0],
+                  rows.stride(0) if rows.shape[0] > 1 else n_t, n_t, _lib.ptr(h_t), int(window_length), _lib.ptr(el_t), _lib.ptr(er_t),
+                  float(divisor), _lib.ptr(out), out.stride(0), _lib.stream_of(dev))
+    out = out.reshape(shape)
+    return out if on_device else out.cpu().numpy()

@@ -287,6 +287,29 @@ int dvh_resample_rows_t(const void* x, int32_t dtype, int32_t n_in, int64_t row_
 int dvh_transpose_f64(const double* src, int64_t n_rows, int64_t n_cols, int64_t src_stride, double* dst,
                       int64_t dst_stride, void* stream);
 
+/* ---------------------------------------------------------------- record ingest
+ * ImagingIO.__getitem__ (modules/imaging_IO.py:37-48) after the file is read: savgol_filter(data, 21, 15) along time
+ * and data /= scale, one pass. */
+
+/* scipy.signal.savgol_filter(x, wlen, order, mode='interp', axis=-1) of rows x[n_rows][n_t] (row_stride elements)
+ * into y (y_stride elements per row, x's dtype: 0 float32, 1 float64; must not overlap x), as three linear maps formed
+ * on the host (das_diff_veh_amd.preprocess.savgol_interp_operator; float64 device tables), half = wlen / 2:
+ *   interior    y[t] = sum_j h[j] x[t - half + j]                        half <= t < n_t - half
+ *   left edge   y[t] = sum_j el[t][j] x[j]                               t < half           (el: half x wlen)
+ *   right edge  y[n_t - half + t] = sum_j er[t][j] x[n_t - wlen + j]     t < half           (er: half x wlen)
+ * Every sum is float64 in tap order j = 0 .. wlen - 1 and rounded once to the output dtype; a sample's value does not
+ * depend on its row, stride or position in a tile.  divisor != 1: the rounded value is then divided in the output dtype
+ * (float32: / (float)divisor, correctly rounded), as ImagingIO's data /= scale.  wlen odd, 3 <= wlen <= 63,
+ * wlen <= n_t <= INT32_MAX - 4096 (-4 otherwise, nothing launched). */
+int dvh_savgol_rows(const void* x, int32_t dtype, int64_t n_rows, int64_t row_stride, int32_t n_t, const double* h,
+                    int32_t wlen, const double* el, const double* er, double divisor, void* y, int64_t y_stride,
+                    void* stream);
+
+/* x[r][t] /= divisor in x's dtype (float32: / (float)divisor), in place, for rows x[n_rows][n_t] (row_stride
+ * elements): ImagingIO's data /= scale on a record that is not smoothed. */
+int dvh_divide_rows(void* x, int32_t dtype, int64_t n_rows, int64_t row_stride, int32_t n_t, double divisor,
+                    void* stream);
+
 /* ---------------------------------------------------------------- vehicle tracking
  * KF_tracking (apis/tracking.py:21-168) on the float64 tracking grid: peak picking per grid row, the detection
  * curve of detect_in_one_section and the association / Kalman loop of tracking_with_veh_base.  The rejection of
