@@ -297,11 +297,6 @@ __global__ __launch_bounds__(64) void ridge_kernel(const float* __restrict__ fv,
   if (lane == 0) status[b] = err;
 }
 
-static int last_launch() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error(-3, hipGetErrorString(e));
-}
-
 }  // namespace dvh
 
 using namespace dvh;

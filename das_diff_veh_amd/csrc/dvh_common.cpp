@@ -15,14 +15,15 @@ int set_error(int code, const char* msg) {
 }
 
 int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-      n = v;
-    if (n <= 0) n = 256;
+  constexpr int kMaxDev = 64;
+  static int cache[kMaxDev] = {};  // by device ordinal; a racing first use stores the same value twice
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return 256;
+  if (cache[dev] == 0) {
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+    cache[dev] = v;
   }
-  return n;
+  return cache[dev];
 }
 }  // namespace dvh
 

@@ -1047,11 +1047,6 @@ __global__ __launch_bounds__(256) void row_l1_kernel(const float* __restrict__ d
   if (threadIdx.x == 0) inv_l1[r] = (float)(1.0 / (part[0] + part[1] + part[2] + part[3]));
 }
 
-static int last_launch() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error(-3, hipGetErrorString(e));
-}
-
 }  // namespace dvh
 
 using namespace dvh;
@@ -1079,15 +1074,12 @@ DVH_API int dvh_disp_tdft(const float* data, int64_t b_stride, int64_t ch_stride
     const void* fn = split ? (const void*)tdft_rows_kernel<kTdNTs, kTdGs> : (const void*)tdft_rows_kernel<kTdNT, 1>;
     const int NT = split ? kTdNTs : kTdNT, G = split ? kTdGs : 1;
     const size_t lds = tdft_rows_lds(NT, G);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return set_error(-3, hipGetErrorString(e));
+    if (int rc = set_dynamic_lds(fn, lds)) return rc;
     dim3 grid((M + kTdRows - 1) / kTdRows, (N + NT * 16 - 1) / (NT * 16));
     void* args[] = {(void*)&data, &b_stride, &ch_stride, &nch, (void*)&M, &nt, (void*)&wt, (void*)&N, (void*)&row_scale, &D};
-    e = hipLaunchKernel(fn, grid, dim3(256 * G), args, lds, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : set_error(-3, hipGetErrorString(e));
+    return hip_status(hipLaunchKernel(fn, grid, dim3(256 * G), args, lds, (hipStream_t)stream));
   }
-  hipError_t e = hipMemsetAsync(D, 0, sizeof(double) * (size_t)M * N, (hipStream_t)stream);
-  if (e != hipSuccess) return set_error(-3, hipGetErrorString(e));
+  if (int rc = hip_status(hipMemsetAsync(D, 0, sizeof(double) * (size_t)M * N, (hipStream_t)stream))) return rc;
   const int tiles = ((M + kGT - 1) / kGT) * ((N + kGT - 1) / kGT);
   // enough K slices for ~1024 waves, at least 64 samples each (more slices measured no faster on
   // 512 gathers: 4 096 / 8 192-wave targets 187 / 188 us vs 167)
@@ -1111,9 +1103,7 @@ DVH_API int dvh_disp_fk(const double* D, int32_t B, int32_t nch, int32_t n_fb, c
   if (B <= 0 || n_fb <= 0) return 0;
   const size_t lds = sizeof(double) * ((size_t)K2 * (kFN + 1) + (size_t)2 * MT * (kFN + 1));
   if (lds > 160 * 1024) return set_error(-4, "too many channels / wavenumbers for one block");
-  hipError_t e = hipFuncSetAttribute((const void*)fk_contract_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds);
-  if (e != hipSuccess) return set_error(-3, hipGetErrorString(e));
+  if (int rc = set_dynamic_lds((const void*)fk_contract_kernel, lds)) return rc;
   dim3 grid((n_fb + kFN - 1) / kFN, B);
   hipLaunchKernelGGL(fk_contract_kernel, grid, dim3(256), lds, (hipStream_t)stream, D, nch, n_fb, atab, MT, K2, n_kb,
                      FK, slot, weight, n_slot);
@@ -1147,9 +1137,7 @@ DVH_API int dvh_disp_fv(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb,
     if (mode && ((work >= 8192 && TO >= 160) || mode > 1) && last >= kSgPad + 1 && TO + 2 * kSgPad <= kTileThreads &&
         nF >= sgl && lds_t <= 64 * 1024) {
       constexpr int VT = kTileVT;
-      hipError_t e = hipFuncSetAttribute((const void*)fv_tile_kernel<VT, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds_t);
-      if (e != hipSuccess) return set_error(-3, hipGetErrorString(e));
+      if (int rc = set_dynamic_lds((const void*)fv_tile_kernel<VT, false>, lds_t)) return rc;
       const int nvc = (nV + VT - 1) / VT;
       const int64_t pairs = (int64_t)nt * nvc;
       int G = (int)((pairs * B + 8191) / 8192);  // ~8 k blocks, at most 64 images each
@@ -1169,9 +1157,7 @@ DVH_API int dvh_disp_fv(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb,
     const size_t lds_b = 2 * sizeof(double) * (size_t)(((size_t)n_kb * n_fb + 1) & ~(size_t)1) +
                          sizeof(double) * (size_t)((sgl * sgl + 1) & ~1) + sizeof(float) * (size_t)VC * (((nF + 3) & ~3) + 2 * kSgPad);
     if ((int64_t)n_kb * n_fb <= (int64_t)kFvPre * kFvThreads && lds_b <= 150 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)fv_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds_b);
-      if (e != hipSuccess) return set_error(-3, hipGetErrorString(e));
+      if (int rc = set_dynamic_lds((const void*)fv_batch_kernel, lds_b)) return rc;
       const int nvc = (nV + VC - 1) / VC;
       // images per block: enough blocks to fill the chip (>= ~2048), at most 16 images each
       // images per block: 1 024 blocks (4 per CU) amortise the per-block weights best (measured
@@ -1191,8 +1177,7 @@ DVH_API int dvh_disp_fv(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb,
   }
   const size_t lds = sizeof(float) * (size_t)nF * kVS;
   if (lds > 160 * 1024) return set_error(-4, "too many frequencies for one block");
-  hipError_t e = hipFuncSetAttribute((const void*)fv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return set_error(-3, hipGetErrorString(e));
+  if (int rc = set_dynamic_lds((const void*)fv_kernel, lds)) return rc;
   dim3 grid((nV + kVC - 1) / kVC, B);
   hipLaunchKernelGGL(fv_kernel, grid, dim3(256), lds, (hipStream_t)stream, FK, n_kb, n_fb, kgrid, kmin, kmax, kq, nF,
                      nV, fj, fw, sg, sgl, fv);
@@ -1222,9 +1207,7 @@ DVH_API int dvh_disp_fv_cells(const double* FK, int32_t B, int32_t n_kb, int32_t
   if (B <= 0 || nV <= 0) return 0;
   const size_t lds = sizeof(double) * (size_t)((max_cell + 1) & ~1) + sizeof(double) * (size_t)((sgl * sgl + 1) & ~1) +
                      sizeof(float) * (size_t)kFvVT * (2 * kSgPad + kTileThreads + 4);
-  hipError_t e = hipFuncSetAttribute((const void*)fv_tile_kernel<kFvVT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds);
-  if (e != hipSuccess) return set_error(-3, hipGetErrorString(e));
+  if (int rc = set_dynamic_lds((const void*)fv_tile_kernel<kFvVT, true>, lds)) return rc;
   const int nvc = (nV + kFvVT - 1) / kFvVT;
   const int64_t pairs = (int64_t)n_tile * nvc;
   int G = (int)((pairs * B + 8191) / 8192);  // ~8 k blocks, at most 64 images each
@@ -1249,8 +1232,7 @@ DVH_API int dvh_disp_fv_mfma(const double* FK, int32_t B, int32_t n_kb, int32_t 
   if (B <= 0 || nV <= 0) return 0;
   constexpr int GI = kMfGI;
   const size_t lds = fv_mfma_lds(GI, n_kb * n_fb);
-  hipError_t e = hipFuncSetAttribute((const void*)fv_mfma_kernel<GI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return set_error(-3, hipGetErrorString(e));
+  if (int rc = set_dynamic_lds((const void*)fv_mfma_kernel<GI>, lds)) return rc;
   const int n_vb = (nV + kMfWaves * kMfV - 1) / (kMfWaves * kMfV);
   if (G <= 0) {  // ~2 k blocks, at most 16 images each, a multiple of GI
     G = (int)(((int64_t)n_vb * B) / 2048);

@@ -189,15 +189,6 @@ __global__ __launch_bounds__(kThreads) void divide_rows_kernel(T* x, int64_t row
   }
 }
 
-template <class T>
-hipError_t launch(const Args& a, int64_t n_blocks, hipStream_t st) {
-  if (a.wlen == 21)
-    savgol_rows_kernel<T, 21><<<dim3((unsigned)n_blocks), dim3(kThreads), 0, st>>>(a);
-  else
-    savgol_rows_kernel<T, 0><<<dim3((unsigned)n_blocks), dim3(kThreads), 0, st>>>(a);
-  return hipGetLastError();
-}
-
 }  // namespace
 
 DVH_API int dvh_savgol_rows(const void* x, int32_t dtype, int64_t n_rows, int64_t row_stride, int32_t n_t,
@@ -233,9 +224,15 @@ DVH_API int dvh_savgol_rows(const void* x, int32_t dtype, int64_t n_rows, int64_
   a.n_tiles = n_tiles;
   a.x_vec = (xa % 16 == 0 && (row_stride * esz) % 16 == 0) ? 1 : 0;
   a.y_vec = (ya % 16 == 0 && (y_stride * esz) % 16 == 0) ? 1 : 0;
-  const hipError_t e = dtype == 0 ? launch<float>(a, n_blocks, (hipStream_t)stream)
-                                  : launch<double>(a, n_blocks, (hipStream_t)stream);
-  return e == hipSuccess ? 0 : set_error(-3, hipGetErrorString(e));
+  return dvh::with_float_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    const dim3 grid((unsigned)n_blocks), block(kThreads);
+    if (wlen == 21)
+      savgol_rows_kernel<T, 21><<<grid, block, 0, (hipStream_t)stream>>>(a);
+    else
+      savgol_rows_kernel<T, 0><<<grid, block, 0, (hipStream_t)stream>>>(a);
+    return dvh::last_launch();
+  });
 }
 
 DVH_API int dvh_divide_rows(void* x, int32_t dtype, int64_t n_rows, int64_t row_stride, int32_t n_t, double divisor,
@@ -248,12 +245,10 @@ DVH_API int dvh_divide_rows(void* x, int32_t dtype, int64_t n_rows, int64_t row_
   int64_t blocks = (total + kThreads - 1) / kThreads;
   const int64_t cap = (int64_t)dvh::cu_count() * 8;
   if (blocks > cap) blocks = cap;
-  if (dtype == 0)
-    divide_rows_kernel<float><<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream>>>(
-        (float*)x, row_stride, n_t, total, divisor);
-  else
-    divide_rows_kernel<double><<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream>>>(
-        (double*)x, row_stride, n_t, total, divisor);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error(-3, hipGetErrorString(e));
+  return dvh::with_float_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    divide_rows_kernel<T><<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream>>>((T*)x, row_stride, n_t,
+                                                                                              total, divisor);
+    return dvh::last_launch();
+  });
 }

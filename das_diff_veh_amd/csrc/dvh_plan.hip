@@ -172,6 +172,5 @@ DVH_API int dvh_pass_geometry(const double* x_axis, int64_t x_stride, const doub
   hipLaunchKernelGGL(pass_geometry_kernel, dim3(n_pass), dim3(block), 0, (hipStream_t)stream, x_axis, x_stride,
                      t_axis, t_stride, n_t, trk_x, trk_t, trk_stride, trk_len, pivot_x, pass_tab, R, delta_t, nsamp,
                      flags, seg_tab, status);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error(-3, hipGetErrorString(e));
+  return last_launch();
 }

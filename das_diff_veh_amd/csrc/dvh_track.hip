@@ -16,11 +16,6 @@
 
 namespace dvh {
 
-static int track_last_launch() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error(-3, hipGetErrorString(e));
-}
-
 // ---------------------------------------------------------------------------------------------
 // Median of |x| per trace by radix select, and the gate.
 //
@@ -257,13 +252,12 @@ DVH_API int dvh_median_abs_gate(void* x, int32_t dtype, int64_t n_rows, int64_t 
   if (n_t == 0) return set_error(-2, "the median of an empty trace is undefined");
   if (n_rows > 0x7fffffffLL) return set_error(-4, "too many traces for one launch");
   const hipStream_t s = (hipStream_t)stream;
-  if (dtype == 0)
-    hipLaunchKernelGGL(median_abs_gate_kernel<float>, dim3((unsigned)n_rows), dim3(kSelBlock), 0, s, (float*)x,
-                       row_stride, n_t, noise_level, med_out, gated_out);
-  else
-    hipLaunchKernelGGL(median_abs_gate_kernel<double>, dim3((unsigned)n_rows), dim3(kSelBlock), 0, s, (double*)x,
-                       row_stride, n_t, noise_level, med_out, gated_out);
-  return track_last_launch();
+  return with_float_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(median_abs_gate_kernel<T>, dim3((unsigned)n_rows), dim3(kSelBlock), 0, s, (T*)x, row_stride,
+                       n_t, noise_level, med_out, gated_out);
+    return last_launch();
+  });
 }
 
 DVH_API int dvh_resample_rows_t(const void* x, int32_t dtype, int32_t n_in, int64_t row_stride, int32_t t_step,
@@ -281,13 +275,12 @@ DVH_API int dvh_resample_rows_t(const void* x, int32_t dtype, int32_t n_in, int6
   if (gy > 65535) return set_error(-4, "too many output rows for one launch");
   const dim3 grid((unsigned)(((int64_t)n_t_out + kRsTT - 1) / kRsTT), (unsigned)gy);
   const hipStream_t s = (hipStream_t)stream;
-  if (dtype == 0)
-    hipLaunchKernelGGL(resample_rows_t_kernel<float>, grid, dim3(kRsTM), 0, s, (const float*)x, n_in, row_stride,
-                       t_step, n_t_out, h, half_len, up, down, out, out_stride, n_out);
-  else
-    hipLaunchKernelGGL(resample_rows_t_kernel<double>, grid, dim3(kRsTM), 0, s, (const double*)x, n_in, row_stride,
-                       t_step, n_t_out, h, half_len, up, down, out, out_stride, n_out);
-  return track_last_launch();
+  return with_float_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(resample_rows_t_kernel<T>, grid, dim3(kRsTM), 0, s, (const T*)x, n_in, row_stride, t_step,
+                       n_t_out, h, half_len, up, down, out, out_stride, n_out);
+    return last_launch();
+  });
 }
 
 DVH_API int dvh_transpose_f64(const double* src, int64_t n_rows, int64_t n_cols, int64_t src_stride, double* dst,
@@ -299,5 +292,5 @@ DVH_API int dvh_transpose_f64(const double* src, int64_t n_rows, int64_t n_cols,
   if (tiles_c * tiles_r > 0x7fffffffLL) return set_error(-4, "too many tiles for one launch");
   hipLaunchKernelGGL(transpose_f64_kernel, dim3((unsigned)(tiles_c * tiles_r)), dim3(256), 0, (hipStream_t)stream, src,
                      n_rows, n_cols, src_stride, dst, dst_stride, tiles_c);
-  return track_last_launch();
+  return last_launch();
 }

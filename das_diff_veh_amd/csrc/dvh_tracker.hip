@@ -15,11 +15,6 @@
 
 namespace dvh {
 
-static int tracker_last_launch() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error(-3, hipGetErrorString(e));
-}
-
 // ---------------------------------------------------------------------------------------------
 // find_peaks of one row per 256-thread block, in SciPy's order: local maxima, distance, prominence.
 //
@@ -356,7 +351,7 @@ DVH_API int dvh_find_peaks_rows(const double* x, int64_t row_stride, int32_t n_t
     hipLaunchKernelGGL(find_peaks_rows_kernel<false>, dim3((unsigned)n_sel), dim3(kPkBlock), lds, s, x, row_stride,
                        n_t, row0, row_step, (double)sign, dist, use_prominence, min_prominence, wl, peaks, cap, count,
                        prominences, status);
-  return tracker_last_launch();
+  return last_launch();
 }
 
 DVH_API int dvh_peak_likelihood(const int32_t* peaks, int32_t cap, const int32_t* count, int32_t n_rows,
@@ -366,7 +361,7 @@ DVH_API int dvh_peak_likelihood(const int32_t* peaks, int32_t cap, const int32_t
   if (n_t == 0) return 0;
   hipLaunchKernelGGL(peak_likelihood_kernel, dim3((unsigned)((n_t + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      peaks, cap, count, n_rows, t_axis, n_t, sigma, out);
-  return tracker_last_launch();
+  return last_launch();
 }
 
 DVH_API int dvh_kf_track(const int32_t* peaks, int32_t cap, const int32_t* count, int32_t n_steps, const double* x_sel,
@@ -376,5 +371,5 @@ DVH_API int dvh_kf_track(const int32_t* peaks, int32_t cap, const int32_t* count
   if (!peaks || !count || !x_sel || !veh_base || !veh_states) return set_error(-2, "null pointer argument");
   hipLaunchKernelGGL(kf_track_kernel, dim3((unsigned)((n_veh + kKfBlock - 1) / kKfBlock)), dim3(kKfBlock), 0,
                      (hipStream_t)stream, peaks, cap, count, n_steps, x_sel, veh_base, n_veh, sigma_a, veh_states);
-  return tracker_last_launch();
+  return last_launch();
 }

@@ -1130,11 +1130,8 @@ static int check_common(const VsgArgs& A) {
 
 static int launch(const void* fn, int grid, int waves, size_t lds, void** args, hipStream_t s) {
   if (grid <= 0) return 0;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return set_error(-3, hipGetErrorString(e));
-  e = hipLaunchKernel(fn, dim3(grid), dim3(64 * waves), args, lds, s);
-  if (e != hipSuccess) return set_error(-3, hipGetErrorString(e));
-  return 0;
+  if (int rc = set_dynamic_lds(fn, lds)) return rc;
+  return hip_status(hipLaunchKernel(fn, dim3(grid), dim3(64 * waves), args, lds, s));
 }
 
 }  // namespace dvh
@@ -1152,8 +1149,7 @@ DVH_API int dvh_window_sumsq(const float* win, int64_t pass_stride, int64_t ch_s
   if (n_pass <= 0) return 0;
   hipLaunchKernelGGL(window_sumsq_kernel, dim3(n_pass), dim3(kBlock), 0, (hipStream_t)stream, win, pass_stride,
                      ch_stride, n_ch, n_t, out);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error(-3, hipGetErrorString(e));
+  return last_launch();
 }
 
 DVH_API int dvh_vsg_scales(const float* win, int64_t pass_stride, int64_t ch_stride, int32_t n_pass,
@@ -1266,8 +1262,7 @@ DVH_API int dvh_vsg_stack_validated(const float* win, int64_t pass_stride, int64
   uint32_t* vflag = work;
   uint32_t* counter = work + S.n_win;
   float2* tab = (table_engine(n) && spec_ws) ? reinterpret_cast<float2*>(spec_ws) : nullptr;
-  hipError_t e = hipMemsetAsync(work, 0, sizeof(uint32_t) * ((size_t)S.n_win + 2), s);
-  if (e != hipSuccess) return set_error(-3, hipGetErrorString(e));
+  if (int rc = hip_status(hipMemsetAsync(work, 0, sizeof(uint32_t) * ((size_t)S.n_win + 2), s))) return rc;
   // the covered-span scan: w = 500's fused engine, default windows, 16-byte aligned rows (the kernel also needs the
   // chunks to list every pass, and falls back to the whole-window scan otherwise).  synth10k launch 13.27-13.28 ->
   // 13.06-13.13 ms, weights 1.304-1.312 -> 1.263-1.289 ms; on the padded engine it lost (w = 499 synth10k 14.8-15.0
@@ -1287,7 +1282,7 @@ DVH_API int dvh_vsg_stack_validated(const float* win, int64_t pass_stride, int64
     if (int rc = launch(v.fn, grid, v.fft + v.scan, v.lds, args, s)) return rc;
     if (span && S.n_win > 0) {  // the windows the covered-span scan could not decide, rescanned whole
       hipLaunchKernelGGL(window_fixup_kernel, dim3((unsigned)S.n_win), dim3(256), 0, s, A, S, vflag);
-      if ((e = hipGetLastError()) != hipSuccess) return set_error(-3, hipGetErrorString(e));
+      if (int rc = last_launch()) return rc;
     }
   } else {  // no fused form: the scan as its own launch, then the plain stack launch
     void* sargs[] = {&A, (void*)&S, &vflag, &counter};
@@ -1300,8 +1295,7 @@ DVH_API int dvh_vsg_stack_validated(const float* win, int64_t pass_stride, int64
   const int64_t slot_elems = (int64_t)R * w;
   hipLaunchKernelGGL(vsg_invalid_fill_kernel, dim3((unsigned)((slot_elems + 4095) / 4096), n_slot), dim3(kFillBlock), 0,
                      s, order, chunk_tab, n_chunk, (const uint32_t*)vflag, unit_scan, stack, slot_elems);
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : set_error(-3, hipGetErrorString(e));
+  return last_launch();
 }
 
 DVH_API int dvh_vsg_stack(const float* win, int64_t pass_stride, int64_t ch_stride, int32_t n_pass,

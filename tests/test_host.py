@@ -147,7 +147,7 @@ def test_library_exports_every_header_symbol():
         build()
     hdr = open(os.path.join(ROOT, "include", "dvh.h")).read()
     declared = set(re.findall(r"^\s*(?:const\s+)?\w+\*?\s+\*?(dvh_\w+)\(", hdr, flags=re.M))
-    assert len(declared) >= 14
+    assert len(declared) == len(_lib.SIGNATURES)
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
@@ -156,6 +156,37 @@ def test_library_exports_every_header_symbol():
     assert _lib.load().dvh_vsg_fft_length(500) == 500
     assert _lib.load().dvh_vsg_fft_length(499) == 1024
     assert _lib.load().dvh_vsg_fft_length(5000) == 0
+
+
+def _ctype_of(decl, returned=False):
+    """The ctypes type of one C parameter (or return) declaration of include/dvh.h; any other spelling fails."""
+    words = re.sub(r"\bconst\b", " ", decl).split()
+    if "*" in decl:  # a returned const char* is a C string, every other pointer an address
+        return ctypes.c_char_p if returned and words[0].rstrip("*") == "char" else ctypes.c_void_p
+    scalars = {"int32_t": ctypes.c_int32, "int": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+               "double": ctypes.c_double}
+    assert len(words) == (1 if returned else 2) and words[0] in scalars, f"no ctypes mapping for {decl!r}"
+    return scalars[words[0]]
+
+
+def test_binding_matches_header():
+    """Every prototype of include/dvh.h against the hand-written ctypes binding: argument count, order and type, and
+    the return type."""
+    from das_diff_veh_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "dvh.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    protos = re.findall(r"([\w \t*]+?)\b(dvh_\w+)\s*\(([^()]*)\)\s*;", hdr)
+    assert len(protos) == len(_lib.SIGNATURES) and {p[1] for p in protos} == set(_lib.SIGNATURES)
+    for ret, name, params in protos:
+        params = [p.strip() for p in params.split(",")]
+        argtypes = [] if params == ["void"] else [_ctype_of(p) for p in params]
+        bound = _lib.SIGNATURES[name]
+        assert len(bound) == len(argtypes), f"{name}: {len(bound)} bound, {len(argtypes)} declared"
+        for i, (b, a) in enumerate(zip(bound, argtypes)):
+            assert b is a, f"{name}: argument {i} ({params[i]!r}) is bound as {b.__name__}"
+        restype = _ctype_of(ret.strip(), returned=True)
+        assert _lib._RESTYPES.get(name, ctypes.c_int32) is restype, f"{name}: return type {ret.strip()!r}"
 
 
 def test_no_cpu_fallback_without_gpu():

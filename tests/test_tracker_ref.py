@@ -4,8 +4,6 @@ own outputs in tests/golden/tracker_*.npz.  No GPU.
 Peak indices, matches and the NaN pattern are integers and must agree exactly; the interpolated samples of the final
 tracks are np.interp of integers (one rounding each way, |value| < 2**10) and are held to 1e-12; the detection curve
 is a sum of a few hundred positive float64 terms computed with the same scipy.stats.norm.pdf, held to 1e-13 max."""
-import os
-
 import numpy as np
 import pytest
 
@@ -104,13 +102,3 @@ def test_restated_pieces_keep_the_quirks():
     full = kr.spread_and_interp(kept)
     assert full.shape == (2, n * 3) and not np.isnan(full).any()
     assert full[1, 18] == pytest.approx((jump[5] + jump[7]) / 2) and full[0, -1] == up[-1]
-
-
-def test_new_entry_points_are_declared():
-    from das_diff_veh_amd import _lib
-    for name, n_args in (("dvh_find_peaks_rows", 17), ("dvh_peak_likelihood", 9), ("dvh_kf_track", 10)):
-        assert len(_lib.SIGNATURES[name]) == n_args, name
-    with open(os.path.join(os.path.dirname(gio.GOLDEN), os.pardir, "include", "dvh.h")) as f:
-        header = f.read()
-    for name in ("dvh_find_peaks_rows", "dvh_peak_likelihood", "dvh_kf_track"):
-        assert name + "(" in header
