@@ -51,6 +51,9 @@ def _check_windows(windows: torch.Tensor, plan: VsgPlan):
         raise ValueError(f"windows must be [n_pass={plan.n_pass}, C, T], got {tuple(windows.shape)}")
     if windows.shape[1] < plan.n_ch or windows.shape[2] < plan.n_t or windows.stride(2) != 1:
         raise ValueError("windows smaller than the plan or time axis not contiguous")
+    # before anything is allocated, zeroed or launched: the library's -4 for a w no engine serves (w > 1024)
+    if int(_lib.load().dvh_vsg_fft_length(plan.w)) == 0:
+        raise ValueError(f"unsupported correlation window length w = {plan.w} (the engines serve 2 <= w <= 1024)")
 
 
 def window_sumsq(windows: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:

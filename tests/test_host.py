@@ -158,6 +158,25 @@ def test_library_exports_every_header_symbol():
     assert _lib.load().dvh_vsg_fft_length(5000) == 0
 
 
+def test_vsg_dispatch_boundaries():
+    """The window length -> transform length dispatch (get_kernels, dvh_vsg.hip) at every boundary between two
+    engines, and the pivot-table workspace, which only the table engines (transform lengths 500 and 1 024) take."""
+    from das_diff_veh_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        from das_diff_veh_amd.build import build
+        build()
+    lib = _lib.load()
+    padded = {2: 512, 256: 512, 257: 1024, 499: 1024, 512: 1024, 513: 2048, 1024: 2048}
+    exact = {250: 250, 500: 500, 1000: 1000}
+    for w, n in {**padded, **exact, 1025: 0, 4096: 0}.items():
+        assert lib.dvh_vsg_fft_length(w) == n, (w, lib.dvh_vsg_fft_length(w), n)
+        nbytes = lib.dvh_vsg_stack_workspace(6, w)
+        assert (nbytes > 0) == (n in (500, 1024)), (w, n, nbytes)
+        if n not in (500, 1024):
+            assert nbytes == 0, (w, nbytes)
+    assert lib.dvh_vsg_stack_workspace(0, 500) == 0
+
+
 def _ctype_of(decl, returned=False):
     """The ctypes type of one C parameter (or return) declaration of include/dvh.h; any other spelling fails."""
     words = re.sub(r"\bconst\b", " ", decl).split()
