@@ -29,38 +29,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
-#include <stdlib.h>
 
 #include <algorithm>
 
 #include "vsg_engines.h"
+#include "vsg_scan.h"
 #include "dvh_common.h"
 #include "dvh.h"
 
 namespace dvh {
 
 constexpr int kBlock = 512;  // sumsq kernel
-// waves per SIMD the kernels are compiled for: the Stockham engines are register-limited to 3,
-// EngF500 fits 4
-template <class E> struct Occ { static constexpr int v = 3; };
-template <> struct Occ<EngF500> { static constexpr int v = 4; };
-// Occupancy target of the stack kernels: 4 waves/SIMD for the exact Stockham engines up to N = 500
-// (their spills at 128 VGPRs sit in the rare time-domain fallback only), else the engine default.
-template <class E> struct OccF {
-  static constexpr int v = E::kWaves == 4 && E::NFFT <= 500 ? 4 : Occ<E>::v;
-};
 
-// The engines with fused first / last stages (FusedOps: EngF500, EngP1024) take a per-pass pivot-slice
-// spectra table in the stack kernels and pack single-sided tasks across passes.
-template <class E> struct Fused { static constexpr bool v = false; };
-template <> struct Fused<EngF500> { static constexpr bool v = true; };
-template <> struct Fused<EngP1024> { static constexpr bool v = true; };
-
-// Per-kernel engine setup: the sub-window length (the padded engines mask their loads with it) and the
-// pivot-slice table (stack kernels; nullptr elsewhere).
+// Per-kernel engine setup of the fused-stage engines (E::kFused: they take a per-pass pivot-slice spectra table in
+// the stack kernels and pack single-sided tasks across passes): the sub-window length (the padded engines mask
+// their loads with it) and the pivot-slice table (stack kernels; nullptr elsewhere).
 template <class E>
 __device__ __forceinline__ void bind_engine(E& e, const VsgArgs& A, const float2* tab) {
-  if constexpr (Fused<E>::v) {
+  if constexpr (E::kFused) {
     e.w = A.w;
     e.tab = tab;
   }
@@ -68,15 +54,15 @@ __device__ __forceinline__ void bind_engine(E& e, const VsgArgs& A, const float2
 
 // One row task's cross spectra: a fused engine with a bound pivot-spectra table uses it (stack kernels).
 template <class E>
-__device__ __forceinline__ void engine_spectra(E& eng, const VsgArgs& A, const RowTask& t, const RowTask& tn,
-                                               bool has_next, float2 (&Cf)[E::NH], float2 (&Co)[E::NH]) {
-  if constexpr (Fused<E>::v) {
+__device__ __forceinline__ void engine_spectra(E& eng, const VsgArgs& A, const RowTask& t, float2 (&Cf)[E::NH],
+                                               float2 (&Co)[E::NH]) {
+  if constexpr (E::kFused) {
     if (eng.tab && eng.tab_usable(t.p, A.n_pass)) {
       eng.spectra_tab(t, A.n_pass, A.hop, Cf, Co);
       return;
     }
   }
-  eng.spectra(t, tn, has_next, A.w, A.hop, Cf, Co);
+  eng.spectra(t, A.w, A.hop, Cf, Co);
 }
 
 // A row task whose passes have only a table-served forward side, transformed across passes.  RAMP: the exact
@@ -85,7 +71,7 @@ template <class E, bool RAMP>
 __device__ __forceinline__ bool engine_direct(E& eng, const VsgArgs& A, const float* scales, const int32_t* order,
                                               const float* weight, int b, int e, int i, float2 (&Gh)[E::NH],
                                               bool* shared = nullptr) {
-  if constexpr (Fused<E>::v) {
+  if constexpr (E::kFused) {
     return eng.tab && eng.template direct_task<RAMP>(A, scales, order, weight, b, e, i, Gh, shared);
   } else {
     return false;
@@ -98,25 +84,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-  return v;
-}
-
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
   return v;
 }
-
-// the next index from a global work counter (one atomic per wave)
-__device__ __forceinline__ int pull_unit(uint32_t* counter, int lane) {
-  int u = 0;
-  if (lane == 0) u = (int)atomicAdd(counter, 1u);
-  return __builtin_amdgcn_readfirstlane(__shfl(u, 0));
-}
-
 
 // XCD-aware block order (blocks are dealt round robin over the 8 XCDs, each with its own L2):
 // consecutive logical blocks -- the row tasks of one pass chunk, which all read that chunk's pivot
@@ -127,13 +99,13 @@ __device__ __forceinline__ int xcd_block() {
   return x < r ? x * (q + 1) + k : r * (q + 1) + (x - r) * q + k;
 }
 
-// The row tasks [0, n) of a stack launch as one wave takes them: a static stride (t0, t0 + stride, ...), or pulled
-// from a global counter.  (Eight per-XCD counters, each XCD draining its own eighth of the tasks before the others'
-// leftovers, measured no faster on the padded engine: w = 499 synth10k launch 15.05 vs 14.99 ms, weights 1.80-1.83
+// The row tasks of a stack launch as one wave takes them: a static stride (t0, t0 + stride, ...), or pulled
+// from a global counter (pull_unit, vsg_scan.h).  (Eight per-XCD counters, each XCD draining its own eighth of the
+// tasks before the others' leftovers, measured no faster on the padded engine: w = 499 synth10k launch 15.05 vs 14.99 ms, weights 1.80-1.83
 // vs 1.81-1.83 ms.)
 struct TaskSource {
   uint32_t* q = nullptr;  // nullptr: static stride
-  int64_t n = 0, stride = 1;
+  int64_t stride = 1;
   __device__ int64_t first(int64_t t0, int lane) { return q ? pull_unit(q, lane) : t0; }
   __device__ int64_t next(int64_t t, int lane) { return q ? pull_unit(q, lane) : t + stride; }
 };
@@ -158,8 +130,8 @@ __device__ __forceinline__ bool window_invalid(const double* __restrict__ sumsq,
 // Per-pass scale of each side: 1 / max(pivot autocorrelation row) after the optional row norm
 // (post_processing_XCF with norm_amp=True); 1 / ||window||_F^2 when neither norm is requested.
 template <class E>
-__global__ __launch_bounds__(64 * E::kWaves, Occ<E>::v) void vsg_scales_kernel(VsgArgs A, const double* __restrict__ sumsq,
-                                                             float* __restrict__ scales) {
+__global__ __launch_bounds__(64 * E::kWaves, E::kOcc) void vsg_scales_kernel(VsgArgs A, const double* __restrict__ sumsq,
+                                                           float* __restrict__ scales) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   E eng = make_engine<E>(lds);
   bind_engine(eng, A, nullptr);
@@ -180,10 +152,7 @@ __global__ __launch_bounds__(64 * E::kWaves, Occ<E>::v) void vsg_scales_kernel(V
       continue;
     }
     const RowTask t = make_task(A, p, uni(A.pass_tab[2 * p + 1] - A.pass_tab[2 * p]));  // the pivot row
-    RowTask tn = t;
-    const bool has_next = norm_amp && p + stride < A.n_pass;
-    if (has_next) tn = make_task(A, p + stride, uni(A.pass_tab[2 * (p + stride) + 1] - A.pass_tab[2 * (p + stride)]));
-    const float2* Y = eng.correlate(t, tn, has_next, A.w, A.hop);
+    const float2* Y = correlate(eng, t, A.w, A.hop);
     float mf = -INFINITY, mo = -INFINITY, sf = 0.f, so = 0.f;
     bool nanf = false, nano = false;
     // a side with nothing accumulated is exactly zero in the reference (the packed inverse FFT
@@ -308,15 +277,14 @@ __device__ __forceinline__ void row_epilogue(const E& eng, const VsgArgs& A, con
 
 template <class E>
 __device__ __forceinline__ void gather_row(E& eng, const VsgArgs& A, const float* __restrict__ scales, int p,
-                                           const RowTask& t, const RowTask& nt, bool has_next, int lane,
-                                           float (&G)[E::NJ]) {
-  const float2* Y = eng.correlate(t, nt, has_next, A.w, A.hop);
+                                           const RowTask& t, int lane, float (&G)[E::NJ]) {
+  const float2* Y = correlate(eng, t, A.w, A.hop);
   row_epilogue<E>(eng, A, Y, t, sld(scales + 2 * p), sld(scales + 2 * p + 1), lane, G);
 }
 
 template <class E>
-__global__ __launch_bounds__(64 * E::kWaves, Occ<E>::v) void vsg_gather_kernel(VsgArgs A, const float* __restrict__ scales,
-                                                             float* __restrict__ out) {
+__global__ __launch_bounds__(64 * E::kWaves, E::kOcc) void vsg_gather_kernel(VsgArgs A, const float* __restrict__ scales,
+                                                           float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   E eng = make_engine<E>(lds);
   bind_engine(eng, A, nullptr);
@@ -328,11 +296,8 @@ __global__ __launch_bounds__(64 * E::kWaves, Occ<E>::v) void vsg_gather_kernel(V
   for (int64_t t = (int64_t)xcd_block() * E::kWaves + wave; t < n_task; t += stride) {
     const int p = uni((int)(t / A.R)), i = uni((int)(t % A.R));
     const RowTask task = make_task(A, p, i);
-    RowTask tn = task;
-    const bool has_next = t + stride < n_task;
-    if (has_next) tn = make_task(A, (int)((t + stride) / A.R), (int)((t + stride) % A.R));
     float G[NJ];
-    gather_row<E>(eng, A, scales, p, task, tn, has_next, lane, G);
+    gather_row<E>(eng, A, scales, p, task, lane, G);
     float* o = out + t * A.w;
 #pragma unroll
     for (int m = 0; m < NJ; ++m) {
@@ -366,7 +331,6 @@ __device__ __forceinline__ void stackf_tasks(E& eng, const VsgArgs& A, const flo
   // tasks from src (static stride or pulled); the next index fetched at the top of the task so that `continue`
   // moves on
   const int lane_t = threadIdx.x & 63;
-  src.n = n_task;
   int64_t tn = src.first(t0, lane_t);
   for (int64_t t = tn; t < n_task; t = tn) {
     tn = src.next(t, lane_t);
@@ -381,7 +345,7 @@ __device__ __forceinline__ void stackf_tasks(E& eng, const VsgArgs& A, const flo
       const int p = sld(order + q);
       const RowTask task = make_task(A, p, i);
       float2 Cf[NH], Co[NH];
-      engine_spectra(eng, A, task, task, false, Cf, Co);
+      engine_spectra(eng, A, task, Cf, Co);
       const float sf = sld(scales + 2 * p), so = sld(scales + 2 * p + 1), wp = sld(weight + p);
       // per-pass bin / twiddle-index math recomputed here (hoisted, it only spills)
       const int lane = opaque(lane_);
@@ -397,7 +361,7 @@ __device__ __forceinline__ void stackf_tasks(E& eng, const VsgArgs& A, const flo
       }
       const bool bad = __ballot(isnan(af + ao)) != 0;
       const bool nzo = other && (__ballot(ao != 0.f) != 0);
-      if constexpr (Fused<E>::v) {  // covered-span scan: a non-finite sample among this pass's loaded slices
+      if constexpr (E::kFused) {  // covered-span scan: a non-finite sample among this pass's loaded slices
         if (eng.vflag && __ballot(!isfinite(af + ao)) != 0 && lane_ == 0) atomicMax(eng.vflag + p, kInfBits);
       }
       float ff, fo;
@@ -502,7 +466,6 @@ __device__ __forceinline__ void stackp_tasks(E& eng, const VsgArgs& A, const flo
   // tasks from src (static stride or pulled); the next index fetched at the top of the task so that `continue`
   // moves on
   const int lane_t = threadIdx.x & 63;
-  src.n = n_task;
   int64_t tn = src.first(t0, lane_t);
   for (int64_t t = tn; t < n_task; t = tn) {
     tn = src.next(t, lane_t);
@@ -529,7 +492,7 @@ __device__ __forceinline__ void stackp_tasks(E& eng, const VsgArgs& A, const flo
       const int p = sld(order + q);
       const RowTask task = make_task(A, p, i);
       float2 Cf[NH], Co[NH];
-      engine_spectra(eng, A, task, task, false, Cf, Co);
+      engine_spectra(eng, A, task, Cf, Co);
       const float sf = sld(scales + 2 * p), so = sld(scales + 2 * p + 1), wp = sld(weight + p);
       const int lane = opaque(lane_);
       float af = 0.f, ao = 0.f;
@@ -542,7 +505,7 @@ __device__ __forceinline__ void stackp_tasks(E& eng, const VsgArgs& A, const flo
       }
       const bool bad = __ballot(isnan(af + ao)) != 0;
       const bool nzo = other && eng.live_o && (__ballot(ao != 0.f) != 0);
-      if constexpr (Fused<E>::v) {  // covered-span scan: a non-finite sample among this pass's loaded slices
+      if constexpr (E::kFused) {  // covered-span scan: a non-finite sample among this pass's loaded slices
         if (eng.vflag && __ballot(!isfinite(af + ao)) != 0 && lane_ == 0) atomicMax(eng.vflag + p, kInfBits);
       }
       float ff = task.nwin_f > 0 ? 1.0f / (float)task.nwin_f : 0.f;
@@ -596,12 +559,9 @@ __device__ __forceinline__ void stackp_tasks(E& eng, const VsgArgs& A, const flo
   }
 }
 
-// occupancy of the padded stack kernel: the N >= 1024 engines hold two accumulated side spectra besides the
-// sub-window's (4 x 9 complex per lane at N = 1024) and would spill at 3 waves / SIMD
-template <class E> struct OccP { static constexpr int v = E::NFFT >= 1000 ? 2 : Occ<E>::v; };
-
+// The plain stack kernels: stackp for the padded engines, stackf for the exact ones (E::kExact).
 template <class E>
-__global__ __launch_bounds__(64 * E::kWaves, OccP<E>::v) void vsg_stackp_kernel(
+__global__ __launch_bounds__(64 * E::kWaves, E::kOccStack) void vsg_stackp_kernel(
     VsgArgs A, const float* __restrict__ scales, const int32_t* __restrict__ order,
     const int32_t* __restrict__ chunk_tab, int32_t n_chunk, const float* __restrict__ weight,
     float* __restrict__ stack, const float2* __restrict__ ptab) {
@@ -615,7 +575,7 @@ __global__ __launch_bounds__(64 * E::kWaves, OccP<E>::v) void vsg_stackp_kernel(
 }
 
 template <class E>
-__global__ __launch_bounds__(64 * E::kWaves, OccF<E>::v) void vsg_stackf_kernel(
+__global__ __launch_bounds__(64 * E::kWaves, E::kOccStack) void vsg_stackf_kernel(
     VsgArgs A, const float* __restrict__ scales, const int32_t* __restrict__ order,
     const int32_t* __restrict__ chunk_tab, int32_t n_chunk, const float* __restrict__ weight,
     float* __restrict__ stack, const float2* __restrict__ ptab) {
@@ -634,7 +594,7 @@ __global__ __launch_bounds__(64 * E::kWaves, OccF<E>::v) void vsg_stackf_kernel(
 // and each slice's non-zero flag at bin kTabBins - 1.
 template <class E>
 __global__ __launch_bounds__(256) void vsg_pivot_table_kernel(VsgArgs A, float2* __restrict__ tab) {
-  constexpr int N = E::N, BINS = E::kTabBins;
+  constexpr int N = E::NFFT, BINS = E::kTabBins;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float2* tw = reinterpret_cast<float2*>(lds);
   init_twiddles<N>(tw);
@@ -720,252 +680,32 @@ __global__ __launch_bounds__(256) void vsg_pivot_table_kernel(VsgArgs A, float2*
 }
 
 // ------------------------------------------------------------------------------------------------
-// Window validity fused into the stack launch.  The reference divides every window by ||data||_F
-// (preprocessing_window, apis/virtual_shot_gather.py:125): a NaN or inf anywhere in the window, or
-// an all-zero window, makes the whole gather NaN (norm / norm_amp divide by a NaN or zero maximum
-// afterwards), and so its class mean.  Deciding that needs every sample of the window, 4x - 130x the
-// bytes the correlations read.  In the validated stack launch, besides the correlation waves, one
-// wave per block streams the windows (16 x 16-byte loads per lane in flight) and keeps the maximum
-// of |x| as a bit pattern, max(bits & 0x7fffffff): >= 0x7f800000 means a NaN / inf, 0 means all
-// zero.  Work is pulled in units of kScanRows channel rows from a global counter, by the scan waves
-// from the start and by the correlation waves once their row tasks are done, so the HBM-bound scan
-// runs under the VALU-bound transforms.  vsg_invalid_fill_kernel then sets the class slots holding an
-// invalid pass to NaN.
-//
-// Scan windows: by default window s is pass s (win + s * pass_stride, n_ch rows), scanned in the
-// correlation's class-sorted order so that both fronts start on the same passes (3.51 vs 3.53 ms per
-// synth10k launch).  A unit launch (plan.UnitPlan: (pass, pivot) units over one flattened record) names
-// its windows instead: scan_tab[s] = first record row of window s, and unit_scan[u] = the window whose
-// flag unit u takes, so a pass imaged at several pivots is validated once per launch.
-constexpr int kScanRows = 16;
-constexpr int kScanDepth = 16;  // 16-byte loads per lane in flight (8 / 12 / 24 measured no better)
-constexpr int kScanAux = 2;     // cache policy of the scan's buffer loads (nt; allocating loads measured 4 % slower on
-                                // synth10k)
-
-__device__ __forceinline__ uint32_t absbits(float x) { return __builtin_bit_cast(uint32_t, x) & 0x7fffffffu; }
-
-
-// Buffer descriptor over [p, p + bytes) built from wave-uniform values (no waterfall loops around the
-// loads); out-of-range loads return 0, which leaves a max |x| unchanged.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t scan_rsrc(const void* p, uint32_t bytes) {
-  const uint64_t a = reinterpret_cast<uint64_t>(p);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-  void* pu = reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(pu, 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// max |x| bit pattern over nf4 consecutive float4 (16-byte aligned): unconditional 16-byte buffer
-// loads, kScanDepth per lane in flight (the descriptor's range check zeroes the tail)
-template <int D = kScanDepth>
-__device__ __forceinline__ uint32_t scan_span(const float* __restrict__ q, int nf4, int lane) {
-  const __amdgpu_buffer_rsrc_t rs = scan_rsrc(q, (uint32_t)nf4 * 16u);
-  const int nsteps = (nf4 + 63) >> 6;
-  uint32_t m = 0;
-  int off = lane * 16;
-  u32x4 r[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-    r[d] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, kScanAux);
-    off += 1024;
-  }
-  for (int s0 = 0; s0 < nsteps; s0 += D) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      const u32x4 v = r[d] & 0x7fffffffu;
-      m = max(m, max(max(v.x, v.y), max(v.z, v.w)));
-      r[d] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, kScanAux);
-      off += 1024;
-    }
-  }
-  return m;
-}
-
-// rows [c0, c1) of a window (n_t samples each): max |x| bit pattern over the wave
-template <int D = kScanDepth>
-__device__ __forceinline__ uint32_t scan_rows(const float* __restrict__ base, int64_t ch_stride, int c0, int c1,
-                                              int n_t, bool vec, int lane) {
-  uint32_t m = 0;
-  if (vec && ch_stride == n_t) {  // the unit's rows are one contiguous span
-    m = scan_span<D>(base + (int64_t)c0 * ch_stride, ((c1 - c0) * n_t) >> 2, lane);
-  } else if (vec) {
-    for (int c = c0; c < c1; ++c) m = max(m, scan_span<D>(base + (int64_t)c * ch_stride, n_t >> 2, lane));
-  } else {
-    for (int c = c0; c < c1; ++c)
-      for (int t = lane; t < n_t; t += 64) m = max(m, absbits(base[(int64_t)c * ch_stride + t]));
-  }
-  return wave_max_u32(m);
-}
-
-struct ScanArgs {
-  const int32_t* tab;  // nullptr: window s = pass s; else first record row of window s
-  int32_t n_win;       // scan windows
-  int32_t n_ch, n_t;   // rows and samples of one window
-};
-
-// ---- covered-span scan: the scan leaves out, per gather row, the float4s inside the row's correlated slices
-// [a, a + (nwin - 1) hop + w) (both sides), which the correlation waves load and validate themselves (non-finite
-// samples reach their spectra, or are checked where a sub-window is not transformed: FusedOps::check_untransformed).
-// A row's remaining float4s are at most three spans; the wave streams them as one virtual index range, each lane's
-// load address mapped past the skipped ranges (two compares), with kScanDepth loads in flight across row boundaries.
-// Windows whose flag ends at 0 (nothing non-zero in the scanned part) or kSuspect are rescanned whole afterwards
-// (window_fixup_kernel), so all-zero windows and non-finite spectra without a pass stay exact.
-struct SpanRow {
-  uint32_t base;  // byte offset of the row in the window (windows < 4 GiB)
-  int U;         // float4s to scan
-  int t0, d0;    // virtual index of the first skipped range, its length (float4)
-  int s1, d1;    // start (real float4 index) and length of the second
-};
-// float4 range wholly inside side (a, L)'s correlated slices (empty when hop > w leaves gaps)
-__device__ __forceinline__ void covered4(int a, int L, int w, int hop, int& b, int& e) {
-  const int nw = n_subwin(L, w, hop);
-  b = e = 0;
-  if (nw <= 0 || hop > w) return;
-  b = (a + 3) >> 2;
-  e = (a + (nw - 1) * hop + w) >> 2;
-  if (e < b) b = e = 0;
-}
-__device__ __forceinline__ SpanRow span_row(const VsgArgs& A, int p, int row0, int c, int n4) {
-  SpanRow r;
-  r.base = (uint32_t)((int64_t)c * A.ch_stride * 4);
-  int b0 = 0, e0 = 0, b1 = 0, e1 = 0;
-  const int i = c - row0;
-  if (i >= 0 && i < A.R) {
-    const int32_t* seg = A.seg_tab + ((int64_t)p * A.R + i) * 4;
-    covered4(sld(seg), sld(seg + 1), A.w, A.hop, b0, e0);
-    if (A.flags & kFlagOtherSide) covered4(sld(seg + 2), sld(seg + 3), A.w, A.hop, b1, e1);
-  }
-  if (e0 <= b0) b0 = e0 = n4;  // empty ranges sit past the row
-  if (e1 <= b1) b1 = e1 = n4;
-  if (b1 < b0) {  // ordered
-    int t = b0; b0 = b1; b1 = t;
-    t = e0; e0 = e1; e1 = t;
-  }
-  if (b1 < e0) {  // overlapping ranges merge
-    e0 = max(e0, e1);
-    b1 = e1 = n4;
-  }
-  e0 = min(e0, n4);
-  e1 = min(e1, n4);
-  r.t0 = b0;
-  r.d0 = e0 - b0;
-  r.s1 = b1;
-  r.d1 = e1 - b1;
-  r.U = n4 - r.d0 - r.d1;
-  if (r.U == 0) r.U = 1;  // a wholly covered row reads one float4 again: no row is empty (one row switch per load)
-  return r;
-}
-// rows [c0, c1) of pass p's window (n_t % 4 == 0, 16-byte aligned rows): max |x| bit pattern over the wave
-// D: loads per lane in flight (the kernel's registers are sized for its correlation waves: EngF500's 128 VGPRs take
-// 11, 12 spill)
-template <int D>
-__device__ __forceinline__ uint32_t scan_rows_span(const VsgArgs& A, const ScanArgs& S, int p, int c0, int c1, int lane) {
-  const float* base = A.win + (int64_t)p * A.pass_stride;
-  const int64_t wbytes = ((int64_t)(S.n_ch - 1) * A.ch_stride + S.n_t) * 4;  // < 0xfffffff0 (host)
-  const __amdgpu_buffer_rsrc_t rs = scan_rsrc(base, (uint32_t)wbytes);
-  const int row0 = sld(A.pass_tab + 2 * p), n4 = S.n_t >> 2;
-  constexpr uint32_t kOut = 0xfffffff0u;  // past the descriptor's range: the load returns 0
-  int c = c0, k = 0;
-  SpanRow cur = span_row(A, p, row0, c, n4);
-  auto issue = [&]() -> uint32_t {
-    if (c < c1 && k * 64 >= cur.U) {  // next row (the loads in flight cover its table reads)
-      ++c;
-      k = 0;
-      if (c < c1) cur = span_row(A, p, row0, c, n4);
-    }
-    if (c >= c1) return kOut;
-    const int v = k * 64 + lane;
-    ++k;
-    int o = v + (v >= cur.t0 ? cur.d0 : 0);
-    o += o >= cur.s1 ? cur.d1 : 0;
-    return v < cur.U ? cur.base + (uint32_t)o * 16u : kOut;
-  };
-  uint32_t m = 0;
-  u32x4 r[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) r[d] = __builtin_amdgcn_raw_buffer_load_b128(rs, issue(), 0, kScanAux);
-  while (c < c1) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      const u32x4 v = r[d] & 0x7fffffffu;
-      m = max(m, max(max(v.x, v.y), max(v.z, v.w)));
-      r[d] = __builtin_amdgcn_raw_buffer_load_b128(rs, issue(), 0, kScanAux);
-    }
-  }
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-    const u32x4 v = r[d] & 0x7fffffffu;
-    m = max(m, max(max(v.x, v.y), max(v.z, v.w)));
-  }
-  return wave_max_u32(m);
-}
-
-// Windows the covered-span scan could not decide -- flag 0 (the scanned part all zero: the slices may not be) or
-// kSuspect -- are rescanned whole: one block per window, nothing to do for the usual flag.
-__global__ __launch_bounds__(256) void window_fixup_kernel(VsgArgs A, ScanArgs S, uint32_t* __restrict__ vflag) {
-  const int s = blockIdx.x;
-  const uint32_t f0 = vflag[s];
-  if (f0 != 0 && !(f0 & kSuspect)) return;
-  __shared__ uint32_t part[4];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float* base = A.win + (int64_t)s * A.pass_stride;
-  uint32_t m = 0;
-  for (int c = wave; c < S.n_ch; c += 4)
-    for (int t = lane; t < S.n_t; t += 64) m = max(m, absbits(base[(int64_t)c * A.ch_stride + t]));
-  m = wave_max_u32(m);
-  if (lane == 0) part[wave] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) vflag[s] = max(max(part[0], part[1]), max(part[2], part[3]));
-}
-
-// Pull scan units (window, kScanRows channel rows) until none is left; atomicMax into vflag[window].  span: the
-// covered-span scan (default windows of a launch whose chunks list every pass), DS loads per lane in flight.
-template <int D = kScanDepth, int DS = 8>
-__device__ __forceinline__ void scan_units(const VsgArgs& A, const ScanArgs& S, uint32_t* __restrict__ vflag,
-                                           uint32_t* __restrict__ counter, int lane,
-                                           const int32_t* __restrict__ sorder = nullptr, bool span = false) {
-  const int upp = (S.n_ch + kScanRows - 1) / kScanRows;  // units per window
-  const int n_units = S.n_win * upp;
-  const bool vec = (S.n_t % 4 == 0) && (A.ch_stride % 4 == 0) && (A.pass_stride % 4 == 0) &&
-                   (reinterpret_cast<uintptr_t>(A.win) % 16 == 0);
-  int u = pull_unit(counter, lane);
-  while (u < n_units) {
-    const int un = pull_unit(counter, lane);  // the next unit's index, fetched under this unit's loads
-    const int q = u / upp, c0 = (u - q * upp) * kScanRows;
-    const int s = (sorder && !S.tab) ? sld(sorder + q) : q;
-    const float* base = S.tab ? A.win + (int64_t)sld(S.tab + s) * A.ch_stride : A.win + (int64_t)s * A.pass_stride;
-    const uint32_t m = span ? scan_rows_span<DS>(A, S, s, c0, min(c0 + kScanRows, S.n_ch), lane)
-                            : scan_rows<D>(base, A.ch_stride, c0, min(c0 + kScanRows, S.n_ch), S.n_t, vec, lane);
-    if (lane == 0) atomicMax(vflag + s, m);
-    u = un;
-  }
-}
-
+// The validated stack launch: the correlation waves and the window validity scan (vsg_scan.h) in one kernel.
 // correlation waves raise their issue priority while they correlate (scan waves stay at 0): the correlation is the
 // critical path; 1 / 2 / 3 all measured 127.7 k -> 136 k windows/s on synth10k
 constexpr int kCorrPrio = 2;
 
 // The row tasks of a stack launch: frequency-domain stacking with the engine's exact (N = w) transforms, or
 // with a zero-padded one (stackp_tasks).
-template <class E, bool EXACT>
+template <class E>
 __device__ __forceinline__ void stack_tasks(E& eng, const VsgArgs& A, const float* __restrict__ scales,
                                             const int32_t* __restrict__ order, const int32_t* __restrict__ chunk_tab,
                                             int32_t n_chunk, const float* __restrict__ weight, float* __restrict__ stack,
                                             int64_t t0, TaskSource src) {
-  if constexpr (EXACT) stackf_tasks<E>(eng, A, scales, order, chunk_tab, n_chunk, weight, stack, t0, src);
+  if constexpr (E::kExact) stackf_tasks<E>(eng, A, scales, order, chunk_tab, n_chunk, weight, stack, t0, src);
   else stackp_tasks<E>(eng, A, scales, order, chunk_tab, n_chunk, weight, stack, t0, src);
 }
 
 // Persistent validated stack launch: blocks of kFft correlation waves + kScan scan waves (EngF500: two per CU;
-// the 1 024-point engines' LDS and registers allow one).
+// the 1 024-point engines' LDS and registers allow one).  EXACT repeats E::kExact: it is part of the kernels'
+// symbol names, which the benchmark and the committed profiles look up.
 template <class E, int kFft, int kScan, int kOcc, bool EXACT = true, int kDepth = kScanDepth, int kSpanDepth = 8>
 __global__ __launch_bounds__(64 * (kFft + kScan), kOcc) void vsg_stackv_kernel(
     VsgArgs A, const float* __restrict__ scales, const int32_t* __restrict__ order,
     const int32_t* __restrict__ chunk_tab, int32_t n_chunk, const float* __restrict__ weight,
     float* __restrict__ stack, ScanArgs S, uint32_t* __restrict__ vflag, uint32_t* __restrict__ counter,
     const float2* __restrict__ ptab, int32_t span_req) {
+  static_assert(EXACT == E::kExact, "EXACT repeats the engine's constant");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   E eng = make_engine<E>(lds);
   bind_engine(eng, A, ptab);
@@ -974,8 +714,8 @@ __global__ __launch_bounds__(64 * (kFft + kScan), kOcc) void vsg_stackv_kernel(
   const int32_t* sorder = (n_chunk > 0 && sld(chunk_tab + 3 * (n_chunk - 1) + 1) == A.n_pass) ? order : nullptr;
   // covered-span scan (the host checked window layout and alignment): every pass's slices are loaded by the
   // correlation only when the chunks list every pass
-  const bool span = Fused<E>::v && span_req && sorder && !S.tab;
-  if constexpr (Fused<E>::v) {
+  const bool span = E::kFused && span_req && sorder && !S.tab;
+  if constexpr (E::kFused) {
     if (span) eng.vflag = vflag;
   }
   // the padded engines' correlation waves pull row tasks (w = 499: fused launch 4.80 -> 3.99 ms, their task costs vary
@@ -983,20 +723,13 @@ __global__ __launch_bounds__(64 * (kFft + kScan), kOcc) void vsg_stackv_kernel(
   // no better: balanced waves all join the scan at once)
   TaskSource src;
   src.stride = (int64_t)gridDim.x * kFft;
-  if constexpr (!EXACT) src.q = counter + 1;
+  if constexpr (!E::kExact) src.q = counter + 1;
   if (wave < kFft) {
     __builtin_amdgcn_s_setprio(kCorrPrio);  // correlation waves issue first when both are ready
-    stack_tasks<E, EXACT>(eng, A, scales, order, chunk_tab, n_chunk, weight, stack, (int64_t)xcd_block() * kFft + wave,
-                          src);
+    stack_tasks<E>(eng, A, scales, order, chunk_tab, n_chunk, weight, stack, (int64_t)xcd_block() * kFft + wave, src);
     __builtin_amdgcn_s_setprio(0);
   }
   scan_units<kDepth, kSpanDepth>(A, S, vflag, counter, lane, sorder, span);
-}
-
-// The validity scan alone (correlation engines without a validated stack kernel).
-__global__ __launch_bounds__(256) void window_scan_kernel(VsgArgs A, ScanArgs S, uint32_t* __restrict__ vflag,
-                                                          uint32_t* __restrict__ counter) {
-  scan_units(A, S, vflag, counter, threadIdx.x & 63);
 }
 
 // stack[slot] = NaN for every slot holding a pass whose window is invalid (vflag NaN / inf or 0).
@@ -1078,48 +811,83 @@ __global__ __launch_bounds__(kBlock) void window_sumsq_kernel(const float* __res
   }
 }
 
-struct VsgKernels {
-  const void* scales;
-  const void* gather;
-  const void* stack;
+// ------------------------------------------------------------------------------------------------
+// The host's engine table: one descriptor per transform length, built from the engine type (engine_row), and the
+// one function from a window length to its descriptor (engine_for).  Everything the entry points launch or size
+// comes from the descriptor; nothing below the table names a transform length or an engine type.
+
+// The validated (correlation + validity scan) launch of a transform length: kernel, correlation / scan waves per
+// block, blocks per CU, LDS per block.  fn == nullptr: no fused form (the scan is its own launch).
+struct VStack {
+  const void* fn;
+  int fft, scan, bpc;
   size_t lds;
+};
+template <class E, int F, int SC, int OCC, int DEPTH = kScanDepth, int SPAN = 8>
+static VStack vstack(int bpc) {
+  return VStack{(const void*)vsg_stackv_kernel<E, F, SC, OCC, E::kExact, DEPTH, SPAN>, F, SC, bpc,
+                E::kBlockBytes + F * E::kWaveBytes};
+}
+
+struct VsgEngine {
+  int nfft;                             // transform length
+  bool exact;                           // serves w == nfft; else every w with 2w - 1 <= nfft (zero padded)
+  const void *scales, *gather, *stack;  // scales, gather and plain stack kernels: `waves` waves, `lds` bytes a block
   int waves;
+  size_t lds;
+  VStack v;                  // validated launch
+  const void* table;         // pivot-slice table kernel (the fused-stage engines), or nullptr
+  size_t table_lds;          // the engine's block tables + 4 waves' buffers (EngP1024's padded buffer A included)
+  int64_t table_pass_bytes;  // table workspace per pass: the entries' spectra and their (start, nwin) head
+  bool span;                 // the covered-span scan may be requested
 };
 
-template <class E, bool EXACT>
-VsgKernels vsg_kernels() {
-  const void* st;
-  if constexpr (EXACT) st = (const void*)vsg_stackf_kernel<E>;
-  else st = (const void*)vsg_stackp_kernel<E>;
-  return VsgKernels{(const void*)vsg_scales_kernel<E>, (const void*)vsg_gather_kernel<E>, st,
-                    E::kBlockBytes + E::kWaves * E::kWaveBytes, E::kWaves};
-}
-
-// Transform length for a window length w: exact mixed-radix when available, else a zero-padded
-// power of two >= 2w - 1 (linear correlation folded back to circular).  Returns 0 if unsupported.
-static int choose_fft(int w, bool* pad) {
-  *pad = false;
-  if (w == 250 || w == 500 || w == 1000) return w;
-  *pad = true;
-  if (2 * w - 1 <= 512) return 512;
-  if (2 * w - 1 <= 1024) return 1024;
-  if (2 * w - 1 <= 2048) return 2048;
-  return 0;
-}
-
-static bool get_kernels(int w, VsgKernels* k, int* n_out) {
-  bool pad;
-  const int n = choose_fft(w, &pad);
-  *n_out = n;
-  switch (n) {
-    case 250: *k = vsg_kernels<EngStockham<250, false>, true>(); return true;
-    case 500: *k = vsg_kernels<EngF500, true>(); return true;  // fused-stage Stockham
-    case 1000: *k = vsg_kernels<EngStockham<1000, false>, true>(); return true;
-    case 512: *k = vsg_kernels<EngStockham<512, true>, false>(); return true;
-    case 1024: *k = vsg_kernels<EngP1024, false>(); return true;  // fused-stage padded Stockham
-    case 2048: *k = vsg_kernels<EngStockham<2048, true>, false>(); return true;
-    default: return false;
+template <class E>
+static VsgEngine engine_row(VStack v = VStack{}, bool span = false) {
+  VsgEngine d{};
+  d.nfft = E::NFFT;
+  d.exact = E::kExact;
+  d.scales = (const void*)vsg_scales_kernel<E>;
+  d.gather = (const void*)vsg_gather_kernel<E>;
+  if constexpr (E::kExact) d.stack = (const void*)vsg_stackf_kernel<E>;
+  else d.stack = (const void*)vsg_stackp_kernel<E>;
+  d.waves = E::kWaves;
+  d.lds = E::kBlockBytes + E::kWaves * E::kWaveBytes;
+  d.v = v;
+  if constexpr (E::kFused) {
+    d.table = (const void*)vsg_pivot_table_kernel<E>;
+    d.table_lds = E::kBlockBytes + 4 * E::kWaveBytes;
+    d.table_pass_bytes = tab_pass_f2<E::kTabBins>() * (int64_t)sizeof(float2) + 2 * kTabEnt * (int64_t)sizeof(int32_t);
   }
+  d.span = span;
+  return d;
+}
+
+// Validated launch shapes.  EngF500: blocks of 7 correlation + 1 scan waves, 2 blocks per CU (4 waves per SIMD, the
+// registers sized for it by the launch bounds).  EngP1024: 7 + 1 waves, one block per CU (LDS, registers), its scan
+// waves keeping 32 loads per lane in flight (w = 499 synth10k launch 14.70 vs 15.08 ms at 16, 14.92 at 48).
+constexpr int kVsFft = 7, kVsScan = 1, kVsBpc = 2, kVsOcc = 4;
+constexpr int kVsSpan = 11;  // the covered-span scan's loads per lane in flight in the EngF500 launch: the most without
+                             // spills (12 spill; 11 vs 8: synth10k 13.06 vs 13.09-13.13 ms, profiles/r6_ab)
+constexpr int kP1Fft = 7, kP1Scan = 1, kP1Depth = 32;
+
+// The engine of window length w: exact mixed-radix when available, else a zero-padded power of two >= 2w - 1 (linear
+// correlation folded back to circular).  nullptr if unsupported.
+// The covered-span scan is requested for EngF500 only: synth10k launch 13.27-13.28 -> 13.06-13.13 ms, weights
+// 1.304-1.312 -> 1.263-1.289 ms; on the padded engine it lost (w = 499 synth10k 14.8-15.0 -> 16.3-17.1 ms at 8 or 16
+// loads per lane in flight against the whole-window scan's 32).
+static const VsgEngine* engine_for(int w) {
+  static const VsgEngine rows[] = {
+      engine_row<EngStockham<250, false>>(),
+      engine_row<EngF500>(vstack<EngF500, kVsFft, kVsScan, kVsOcc, kScanDepth, kVsSpan>(kVsBpc), /*span=*/true),
+      engine_row<EngStockham<1000, false>>(),
+      engine_row<EngStockham<512, true>>(vstack<EngStockham<512, true>, 7, 1, 2>(1)),
+      engine_row<EngP1024>(vstack<EngP1024, kP1Fft, kP1Scan, 2, kP1Depth>(1)),
+      engine_row<EngStockham<2048, true>>(),
+  };
+  for (const VsgEngine& e : rows)  // the exact rows first
+    if (e.exact ? w == e.nfft : 2 * w - 1 <= e.nfft) return &e;
+  return nullptr;
 }
 
 static int check_common(const VsgArgs& A) {
@@ -1134,13 +902,50 @@ static int launch(const void* fn, int grid, int waves, size_t lds, void** args, 
   return hip_status(hipLaunchKernel(fn, dim3(grid), dim3(64 * waves), args, lds, s));
 }
 
+// The entry points' common start: the geometry, then the entry point's own argument check (arg_error: its message,
+// or nullptr), then the engine of the window length -- refused before anything is launched or zeroed.
+struct VsgCall {
+  VsgArgs A;
+  const VsgEngine* eng;
+  int rc;
+};
+static VsgCall vsg_begin(const VsgArgs& A, const char* arg_error) {
+  VsgCall c{A, nullptr, 0};
+  if ((c.rc = check_common(A))) return c;
+  if (arg_error) c.rc = set_error(-2, arg_error);
+  else if (!(c.eng = engine_for(A.w))) c.rc = set_error(-4, "unsupported correlation window length");
+  return c;
+}
+
+// blocks of `waves` waves, one task per wave (the launches stride over what the clamp leaves)
+static int task_grid(int64_t tasks, int waves) {
+  const int64_t grid = (tasks + waves - 1) / waves;
+  return (int)(grid > (1 << 30) ? (1 << 30) : grid);
+}
+
+static int launch_table(const VsgEngine& e, VsgArgs& A, float2* tab, hipStream_t s) {
+  const int grid = (int)std::min<int64_t>(((int64_t)A.n_pass + 3) / 4, 8 * (int64_t)cu_count());
+  void* args[] = {&A, &tab};
+  return launch(e.table, grid, 4, e.table_lds, args, s);
+}
+
+// The pivot-slice table if one is given, then the plain stack launch.
+static int launch_stack(const VsgEngine& e, VsgArgs& A, const float* scales, const int32_t* order,
+                        const int32_t* chunk_tab, int32_t n_chunk, const float* weight, float* stack, float2* tab,
+                        hipStream_t s) {
+  if (tab)
+    if (int rc = launch_table(e, A, tab, s)) return rc;
+  void* args[] = {&A, &scales, &order, &chunk_tab, &n_chunk, &weight, &stack, &tab};
+  return launch(e.stack, task_grid((int64_t)n_chunk * A.R, e.waves), e.waves, e.lds, args, s);
+}
+
 }  // namespace dvh
 
 using namespace dvh;
 
 DVH_API int dvh_vsg_fft_length(int32_t w) {
-  bool pad;
-  return choose_fft(w, &pad);
+  const VsgEngine* e = engine_for(w);
+  return e ? e->nfft : 0;
 }
 
 DVH_API int dvh_window_sumsq(const float* win, int64_t pass_stride, int64_t ch_stride, int32_t n_pass, int32_t n_ch,
@@ -1155,89 +960,32 @@ DVH_API int dvh_window_sumsq(const float* win, int64_t pass_stride, int64_t ch_s
 DVH_API int dvh_vsg_scales(const float* win, int64_t pass_stride, int64_t ch_stride, int32_t n_pass,
                            const int32_t* pass_tab, const int32_t* seg_tab, int32_t R, int32_t w, int32_t hop,
                            int32_t flags, const double* win_sumsq, float* scales, void* stream) {
-  VsgArgs A{win, pass_stride, ch_stride, pass_tab, seg_tab, n_pass, R, w, hop, flags};
-  if (int rc = check_common(A)) return rc;
-  if (!scales) return set_error(-2, "null scales");
-  if (!(flags & kFlagNormAmp) && !(flags & kFlagNorm) && !win_sumsq)
-    return set_error(-2, "win_sumsq required when norm and norm_amp are both off");
-  VsgKernels k;
-  int n;
-  if (!get_kernels(w, &k, &n)) return set_error(-4, "unsupported correlation window length");
-  void* args[] = {&A, &win_sumsq, &scales};
-  return launch(k.scales, (n_pass + k.waves - 1) / k.waves, k.waves, k.lds, args, (hipStream_t)stream);
+  VsgCall c = vsg_begin({win, pass_stride, ch_stride, pass_tab, seg_tab, n_pass, R, w, hop, flags},
+                        !scales ? "null scales"
+                        : (!(flags & kFlagNormAmp) && !(flags & kFlagNorm) && !win_sumsq)
+                            ? "win_sumsq required when norm and norm_amp are both off"
+                            : nullptr);
+  if (c.rc) return c.rc;
+  const VsgEngine& e = *c.eng;
+  void* args[] = {&c.A, &win_sumsq, &scales};
+  return launch(e.scales, task_grid(n_pass, e.waves), e.waves, e.lds, args, (hipStream_t)stream);
 }
 
 DVH_API int dvh_vsg_gathers(const float* win, int64_t pass_stride, int64_t ch_stride, int32_t n_pass,
                             const int32_t* pass_tab, const int32_t* seg_tab, int32_t R, int32_t w, int32_t hop,
                             int32_t flags, const float* scales, float* out, void* stream) {
-  VsgArgs A{win, pass_stride, ch_stride, pass_tab, seg_tab, n_pass, R, w, hop, flags};
-  if (int rc = check_common(A)) return rc;
-  if (!scales || !out) return set_error(-2, "null pointer argument");
-  VsgKernels k;
-  int n;
-  if (!get_kernels(w, &k, &n)) return set_error(-4, "unsupported correlation window length");
-  const int64_t tasks = (int64_t)n_pass * R;
-  const int64_t grid = (tasks + k.waves - 1) / k.waves;
-  void* args[] = {&A, &scales, &out};
-  return launch(k.gather, (int)(grid > (1 << 30) ? (1 << 30) : grid), k.waves, k.lds, args, (hipStream_t)stream);
-}
-
-// Validated launch shapes.  EngF500: blocks of 7 correlation + 1 scan waves, 2 blocks per CU (4 waves per SIMD, the
-// registers sized for it by the launch bounds).  EngP1024: 7 + 1 waves, one block per CU (LDS, registers), its scan
-// waves keeping 32 loads per lane in flight (w = 499 synth10k launch 14.70 vs 15.08 ms at 16, 14.92 at 48).
-constexpr int kVsFft = 7, kVsScan = 1, kVsBpc = 2, kVsOcc = 4;
-constexpr int kVsSpan = 11;  // the covered-span scan's loads per lane in flight in the EngF500 launch: the most without
-                             // spills (12 spill; 11 vs 8: synth10k 13.06 vs 13.09-13.13 ms, profiles/r6_ab)
-constexpr int kP1Fft = 7, kP1Scan = 1, kP1Depth = 32;
-
-// The fused (correlation + validity scan) launch of each transform length: kernel, correlation / scan waves per
-// block, blocks per CU, LDS per block.
-struct VStack {
-  const void* fn;
-  int fft, scan, bpc;
-  size_t lds;
-};
-template <class E, int F, int SC, int OCC, bool EXACT, int DEPTH = kScanDepth, int SPAN = 8>
-static VStack vstack(int bpc) {
-  return VStack{(const void*)vsg_stackv_kernel<E, F, SC, OCC, EXACT, DEPTH, SPAN>, F, SC, bpc,
-                E::kBlockBytes + F * E::kWaveBytes};
-}
-static bool get_vstack(int n, VStack* v) {
-  switch (n) {
-    case 500: *v = vstack<EngF500, kVsFft, kVsScan, kVsOcc, true, kScanDepth, kVsSpan>(kVsBpc); return true;
-    case 512: *v = vstack<EngStockham<512, true>, 7, 1, 2, false>(1); return true;
-    case 1024: *v = vstack<EngP1024, kP1Fft, kP1Scan, 2, false, kP1Depth>(1); return true;
-    default: return false;
-  }
-}
-
-// Transform lengths whose engine takes the pivot-slice table: 500 (EngF500) and the padded 1 024 (EngP1024).
-static bool table_engine(int n) { return n == 500 || n == 1024; }
-
-template <class E>
-static int64_t table_bytes(int64_t n_pass) {
-  return n_pass * (tab_pass_f2<E::kTabBins>() * (int64_t)sizeof(float2) + 2 * kTabEnt * (int64_t)sizeof(int32_t));
-}
-static int64_t stack_ws_bytes(int n, int64_t n_pass) {
-  return n == 500 ? table_bytes<EngF500>(n_pass) : table_bytes<EngP1024>(n_pass);
-}
-
-static int launch_table(VsgArgs& A, int n, float2* tab, hipStream_t s) {
-  const int grid = (int)std::min<int64_t>(((int64_t)A.n_pass + 3) / 4, 8 * (int64_t)cu_count());
-  void* args[] = {&A, &tab};
-  // the engine's block tables + 4 waves' buffers (EngP1024's padded buffer A and stage tables included)
-  if (n == 500)
-    return launch((const void*)vsg_pivot_table_kernel<EngF500>, grid, 4, EngF500::kBlockBytes + 4 * EngF500::kWaveBytes,
-                  args, s);
-  return launch((const void*)vsg_pivot_table_kernel<EngP1024>, grid, 4, EngP1024::kBlockBytes + 4 * EngP1024::kWaveBytes,
-                args, s);
+  VsgCall c = vsg_begin({win, pass_stride, ch_stride, pass_tab, seg_tab, n_pass, R, w, hop, flags},
+                        (!scales || !out) ? "null pointer argument" : nullptr);
+  if (c.rc) return c.rc;
+  const VsgEngine& e = *c.eng;
+  void* args[] = {&c.A, &scales, &out};
+  return launch(e.gather, task_grid((int64_t)n_pass * R, e.waves), e.waves, e.lds, args, (hipStream_t)stream);
 }
 
 DVH_API int64_t dvh_vsg_stack_workspace(int32_t n_pass, int32_t w) {
-  bool pad;
-  const int n = choose_fft(w, &pad);
-  if (n_pass <= 0 || !table_engine(n)) return 0;
-  return stack_ws_bytes(n, n_pass);
+  const VsgEngine* e = engine_for(w);
+  if (n_pass <= 0 || !e || !e->table) return 0;
+  return n_pass * e->table_pass_bytes;
 }
 
 DVH_API int dvh_vsg_stack_validated(const float* win, int64_t pass_stride, int64_t ch_stride, int32_t n_pass,
@@ -1246,37 +994,34 @@ DVH_API int dvh_vsg_stack_validated(const float* win, int64_t pass_stride, int64
                                     const int32_t* chunk_tab, int32_t n_chunk, int32_t n_slot, const float* weight,
                                     float* stack, const int32_t* scan_tab, int32_t n_scan, const int32_t* unit_scan,
                                     uint32_t* work, void* spec_ws, void* stream) {
-  VsgArgs A{win, pass_stride, ch_stride, pass_tab, seg_tab, n_pass, R, w, hop, flags};
-  if (int rc = check_common(A)) return rc;
-  if (!scales || !order || !chunk_tab || !weight || !stack || !work) return set_error(-2, "null pointer argument");
-  if (!(flags & (kFlagNorm | kFlagNormAmp)))
-    return set_error(-2, "validated stacking needs norm or norm_amp (raw scales need ||data||_F: dvh_window_sumsq)");
-  if (n_ch < R || n_t <= 0) return set_error(-2, "window smaller than the gather");
-  if ((scan_tab == nullptr) != (unit_scan == nullptr)) return set_error(-2, "scan_tab and unit_scan go together");
-  if (scan_tab && n_scan <= 0) return set_error(-2, "a scan table needs n_scan > 0");
-  VsgKernels k;
-  int n;
-  if (!get_kernels(w, &k, &n)) return set_error(-4, "unsupported correlation window length");
+  VsgCall c = vsg_begin(
+      {win, pass_stride, ch_stride, pass_tab, seg_tab, n_pass, R, w, hop, flags},
+      (!scales || !order || !chunk_tab || !weight || !stack || !work) ? "null pointer argument"
+      : !(flags & (kFlagNorm | kFlagNormAmp))
+          ? "validated stacking needs norm or norm_amp (raw scales need ||data||_F: dvh_window_sumsq)"
+      : (n_ch < R || n_t <= 0)                             ? "window smaller than the gather"
+      : ((scan_tab == nullptr) != (unit_scan == nullptr)) ? "scan_tab and unit_scan go together"
+      : (scan_tab && n_scan <= 0)                          ? "a scan table needs n_scan > 0"
+                                                           : nullptr);
+  if (c.rc) return c.rc;
+  const VsgEngine& e = *c.eng;
+  VsgArgs& A = c.A;
   const ScanArgs S{scan_tab, scan_tab ? n_scan : n_pass, n_ch, n_t};
   hipStream_t s = (hipStream_t)stream;
   uint32_t* vflag = work;
   uint32_t* counter = work + S.n_win;
-  float2* tab = (table_engine(n) && spec_ws) ? reinterpret_cast<float2*>(spec_ws) : nullptr;
+  float2* tab = (e.table && spec_ws) ? reinterpret_cast<float2*>(spec_ws) : nullptr;
   if (int rc = hip_status(hipMemsetAsync(work, 0, sizeof(uint32_t) * ((size_t)S.n_win + 2), s))) return rc;
-  // the covered-span scan: w = 500's fused engine, default windows, 16-byte aligned rows (the kernel also needs the
-  // chunks to list every pass, and falls back to the whole-window scan otherwise).  synth10k launch 13.27-13.28 ->
-  // 13.06-13.13 ms, weights 1.304-1.312 -> 1.263-1.289 ms; on the padded engine it lost (w = 499 synth10k 14.8-15.0
-  // -> 16.3-17.1 ms at 8 or 16 loads per lane in flight against the whole-window scan's 32).  DVH_SCAN_SPAN=0: off.
-  static const int span_env = getenv("DVH_SCAN_SPAN") ? atoi(getenv("DVH_SCAN_SPAN")) : 1;
-  int32_t span = (span_env && n == 500 && !scan_tab && n_t % 4 == 0 && ch_stride % 4 == 0 && pass_stride % 4 == 0 &&
+  // the covered-span scan: an engine that allows it, default windows, 16-byte aligned rows (the kernel also needs the
+  // chunks to list every pass, and falls back to the whole-window scan otherwise)
+  int32_t span = (e.span && !scan_tab && n_t % 4 == 0 && ch_stride % 4 == 0 && pass_stride % 4 == 0 &&
                   reinterpret_cast<uintptr_t>(win) % 16 == 0 &&
                   ((int64_t)(n_ch - 1) * ch_stride + n_t) * 4 < 0xfffffff0LL) ? 1 : 0;
-  if (tab)
-    if (int rc = launch_table(A, n, tab, s)) return rc;
-  const int64_t tasks = (int64_t)n_chunk * R;
-  VStack v{};
-  if (get_vstack(n, &v)) {
-    const int64_t need = (tasks + v.fft - 1) / v.fft;
+  if (e.v.fn) {
+    if (tab)
+      if (int rc = launch_table(e, A, tab, s)) return rc;
+    const VStack& v = e.v;
+    const int64_t need = ((int64_t)n_chunk * R + v.fft - 1) / v.fft;
     const int grid = (int)(need < v.bpc * cu_count() ? (need > 0 ? need : 1) : v.bpc * cu_count());
     void* args[] = {&A, &scales, &order, &chunk_tab, &n_chunk, &weight, &stack, (void*)&S, &vflag, &counter, &tab, &span};
     if (int rc = launch(v.fn, grid, v.fft + v.scan, v.lds, args, s)) return rc;
@@ -1287,9 +1032,7 @@ DVH_API int dvh_vsg_stack_validated(const float* win, int64_t pass_stride, int64
   } else {  // no fused form: the scan as its own launch, then the plain stack launch
     void* sargs[] = {&A, (void*)&S, &vflag, &counter};
     if (int rc = launch((const void*)window_scan_kernel, 4 * cu_count(), 4, 0, sargs, s)) return rc;
-    const int64_t grid = (tasks + k.waves - 1) / k.waves;
-    void* args[] = {&A, &scales, &order, &chunk_tab, &n_chunk, &weight, &stack, &tab};
-    if (int rc = launch(k.stack, (int)(grid > (1 << 30) ? (1 << 30) : grid), k.waves, k.lds, args, s)) return rc;
+    if (int rc = launch_stack(e, A, scales, order, chunk_tab, n_chunk, weight, stack, tab, s)) return rc;
   }
   if (n_slot <= 0 || n_chunk <= 0) return 0;
   const int64_t slot_elems = (int64_t)R * w;
@@ -1302,18 +1045,9 @@ DVH_API int dvh_vsg_stack(const float* win, int64_t pass_stride, int64_t ch_stri
                           const int32_t* pass_tab, const int32_t* seg_tab, int32_t R, int32_t w, int32_t hop,
                           int32_t flags, const float* scales, const int32_t* order, const int32_t* chunk_tab,
                           int32_t n_chunk, const float* weight, float* stack, void* spec_ws, void* stream) {
-  VsgArgs A{win, pass_stride, ch_stride, pass_tab, seg_tab, n_pass, R, w, hop, flags};
-  if (int rc = check_common(A)) return rc;
-  if (!scales || !order || !chunk_tab || !weight || !stack) return set_error(-2, "null pointer argument");
-  VsgKernels k;
-  int n;
-  if (!get_kernels(w, &k, &n)) return set_error(-4, "unsupported correlation window length");
-  const int64_t tasks = (int64_t)n_chunk * R;
-  hipStream_t s = (hipStream_t)stream;
-  float2* tab = (table_engine(n) && spec_ws) ? reinterpret_cast<float2*>(spec_ws) : nullptr;
-  if (tab)
-    if (int rc = launch_table(A, n, tab, s)) return rc;
-  const int64_t grid = (tasks + k.waves - 1) / k.waves;
-  void* args[] = {&A, &scales, &order, &chunk_tab, &n_chunk, &weight, &stack, &tab};
-  return launch(k.stack, (int)(grid > (1 << 30) ? (1 << 30) : grid), k.waves, k.lds, args, s);
+  VsgCall c = vsg_begin({win, pass_stride, ch_stride, pass_tab, seg_tab, n_pass, R, w, hop, flags},
+                        (!scales || !order || !chunk_tab || !weight || !stack) ? "null pointer argument" : nullptr);
+  if (c.rc) return c.rc;
+  float2* tab = (c.eng->table && spec_ws) ? reinterpret_cast<float2*>(spec_ws) : nullptr;
+  return launch_stack(*c.eng, c.A, scales, order, chunk_tab, n_chunk, weight, stack, tab, (hipStream_t)stream);
 }

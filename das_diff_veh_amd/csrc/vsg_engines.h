@@ -20,6 +20,14 @@
 //   EngP1024             w <= 512 without an exact engine (w = 499): zero-padded 4^5 transform, first and
 //                        last stages in registers, as EngF500 (pivot-slice table, cross-pass packing).
 // (Engine variants measured and not kept are listed in DESIGN.md.)
+//
+// Each engine states its own facts once, as constants the kernels and the host's engine table (dvh_vsg.hip) read:
+//   NFFT       the transform length;
+//   kExact     NFFT = w (stackf_tasks), else NFFT >= 2w - 1 zero padded (stackp_tasks, the fold in corr_at());
+//   kFused     a FusedOps engine: takes the pivot-slice table and packs single-sided tasks across passes;
+//   kOcc       waves / SIMD its scales and gather kernels are compiled for;
+//   kOccStack  waves / SIMD its plain stack kernel is compiled for;
+//   kWaves     waves per block;  NJ: lags per lane in the epilogues;  NH: half-spectrum slots per lane.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -114,7 +122,7 @@ __device__ __forceinline__ int opaque(int v) {
 __device__ __forceinline__ uint32_t nzbits(float x) { return __builtin_bit_cast(uint32_t, x) & 0x7fffffffu; }
 // OR-accumulated non-zero bits of the loaded samples (one v_and_or per sample)
 __device__ __forceinline__ uint32_t maxbits(uint32_t b, float x) { return b | nzbits(x); }
-// Validity flags of the covered-span scan (dvh_vsg.hip): per pass the max |x| bit pattern of the samples the scan
+// Validity flags of the covered-span scan (vsg_scan.h): per pass the max |x| bit pattern of the samples the scan
 // read (>= kInfBits: a NaN / inf), or'ed with kSuspect when a correlation wave saw a non-finite spectrum it cannot
 // attribute to one pass (the window is then rescanned whole).
 constexpr uint32_t kInfBits = 0x7f800000u, kSuspect = 0x80000000u;
@@ -138,10 +146,32 @@ __device__ __forceinline__ void store_conj_hermitian(float2* buf, const float2 (
   for (int j = 0; j < E::NH; ++j) {
     const int f = E::bin(lane, j);
     if (f >= 0) {
-      buf[E::slot(f)] = make_float2(Cf[j].x - Co[j].y, -(Cf[j].y + Co[j].x));
-      if (f > 0 && f < N / 2) buf[E::slot(N - f)] = make_float2(Cf[j].x + Co[j].y, Cf[j].y - Co[j].x);
+      buf[f] = make_float2(Cf[j].x - Co[j].y, -(Cf[j].y + Co[j].x));
+      if (f > 0 && f < N / 2) buf[N - f] = make_float2(Cf[j].x + Co[j].y, Cf[j].y - Co[j].x);
     }
   }
+}
+
+// One row task's correlations: the accumulated cross spectra of both sides, then the one inverse transform.
+// Returns Y with Y[k].x = N * IDFT(Cf)[k], -Y[k].y = N * IDFT(Co)[k], read through E::c().
+template <class E>
+__device__ __forceinline__ const float2* correlate(E& eng, const RowTask& t, int w, int hop) {
+  float2 Cf[E::NH], Co[E::NH];
+  eng.spectra(t, w, hop, Cf, Co);
+  return eng.inverse(Cf, Co);
+}
+
+// (N * sum_s c_f[k], N * sum_s c_o[k]) at lag k of the inverse transform's output Y.  PAD: the linear correlation
+// of the zero-padded sub-windows folded to the circular one of period w.
+template <int N, bool PAD>
+__device__ __forceinline__ float2 corr_at(const float2* Y, int k, int w) {
+  float2 v = Y[k];
+  if (PAD && k > 0) {
+    const float2 u = Y[N - w + k];
+    v.x += u.x;
+    v.y += u.y;
+  }
+  return make_float2(v.x, -v.y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -149,7 +179,13 @@ template <int N, bool PAD>
 struct EngStockham {
   static constexpr int NFFT = N;
   static constexpr int kWaves = 4;
-  static constexpr bool kNextTask = false;
+  static constexpr bool kExact = !PAD;
+  static constexpr bool kFused = false;
+  static constexpr int kOcc = 3;  // register-limited to 3 waves / SIMD
+  // plain stack kernel: 4 for the exact transforms up to N = 500 (their spills at 128 VGPRs sit in the rare
+  // time-domain fallback only); the padded N >= 1024 hold two accumulated side spectra besides the sub-window's
+  // and would spill at 3
+  static constexpr int kOccStack = PAD ? (N >= 1024 ? 2 : kOcc) : (N <= 500 ? 4 : kOcc);
   static constexpr int NJ = (N + 63) / 64;
   static constexpr int NH = (N / 2 + 1 + 63) / 64;
   static_assert(N % 2 == 0, "Hermitian half spectra assume an even length");
@@ -180,8 +216,7 @@ struct EngStockham {
   }
 
   // accumulated cross spectra of both sides: Cf[j], Co[j] at bins f = lane + 64 j
-  __device__ void spectra(const RowTask& t, const RowTask&, bool, int w, int hop, float2 (&Cf)[NH],
-                          float2 (&Co)[NH]) {
+  __device__ void spectra(const RowTask& t, int w, int hop, float2 (&Cf)[NH], float2 (&Co)[NH]) {
     const int nq = t.nwin_f + t.nwin_o;
     float2 z[NZ];
 #pragma unroll
@@ -234,39 +269,23 @@ struct EngStockham {
     }
   }
 
-  // Y with Y[k].x = N * IDFT(Cf)[k], -Y[k].y = N * IDFT(Co)[k] (read through c())
   // half-spectrum slot j of a lane holds bin f = lane + 64 j (f <= N/2)
   static __device__ __forceinline__ int bin(int lane, int j) {
     const int f = lane + 64 * j;
     return f <= N / 2 ? f : -1;
   }
-  static __device__ __forceinline__ int slot(int n) { return n; }
 
+  // Y with Y[k].x = N * IDFT(Cf)[k], -Y[k].y = N * IDFT(Co)[k] (read through c())
   __device__ const float2* inverse(const float2 (&Cf)[NH], const float2 (&Co)[NH]) {
     store_conj_hermitian<EngStockham>(bufA, Cf, Co, lane);
     wave_sync();
     return FftPlan<N>::T::run(bufA, bufB, tw, lane);
   }
 
-  __device__ const float2* correlate(const RowTask& t, const RowTask& nt, bool has_next, int w, int hop) {
-    float2 Cf[NH], Co[NH];
-    this->spectra(t, nt, has_next, w, hop, Cf, Co);
-    return inverse(Cf, Co);
-  }
-
   // twiddle exp(-2 pi i m / N), m in [0, N)
   __device__ float2 twiddle(int m) const { return tw[m]; }
 
-  // (N * sum_s c_f[k], N * sum_s c_o[k])
-  __device__ float2 c(const float2* Y, int k, int w) const {
-    float2 v = Y[k];
-    if (PAD && k > 0) {
-      const float2 u = Y[N - w + k];
-      v.x += u.x;
-      v.y += u.y;
-    }
-    return make_float2(v.x, -v.y);
-  }
+  __device__ float2 c(const float2* Y, int k, int w) const { return corr_at<N, PAD>(Y, k, w); }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -303,7 +322,7 @@ __device__ __forceinline__ const int32_t* tab_head(const float2* tab, int n_pass
 
 // ------------------------------------------------------------------------------------------------
 // FusedOps<E>: the row-task logic of the engines whose first and last transform stages run in registers
-// (EngF500, EngP1024).  E provides the transform: N / NFFT, kNJ (sample registers per lane; not E::NJ, the
+// (EngF500, EngP1024).  E provides the transform: NFFT, kNJ (E::kNZ, the sample registers per lane; not E::NJ, the
 // lags per lane of the epilogues in dvh_vsg.hip), NH (half-spectrum slots per lane), kTabBins, bin(l, j),
 // load_ri() (a sub-window's samples into registers), stage1() (registers -> LDS), finish_with(acc) (the remaining stages, then acc(j, Z[f], Z[N - f]) for every half-spectrum slot j
 // of the lane), inverse() and c() (the correlation at lag k after the inverse).  FusedOps holds the per-wave
@@ -371,8 +390,7 @@ struct FusedOps {
   }
 
   // Sub-window q's pivot and receiver samples are loaded one sub-window ahead.
-  __device__ void spectra(const RowTask& t, const RowTask&, bool, int, int hop, float2 (&Cf)[kNH],
-                          float2 (&Co)[kNH]) {
+  __device__ void spectra(const RowTask& t, int, int hop, float2 (&Cf)[kNH], float2 (&Co)[kNH]) {
     constexpr int NH_ = kNH;
     const int nq = t.nwin_f + t.nwin_o;
 #pragma unroll
@@ -719,27 +737,28 @@ struct FusedOps {
 // Half-spectrum slots per lane l: j < 3 -> f = l + 100 j (l <= 50); j = 3, 4 -> f = 100 - l + 100 (j - 3)
 // (1 <= l <= 49): each of the 251 bins f <= 250 exactly once.
 struct EngF500 : FusedOps<EngF500, 10, 5> {
-  static constexpr int N = 500;
   static constexpr int NFFT = 500;
   static constexpr int NJ = 8;   // lags per lane in the epilogues (dvh_vsg.hip)
   static constexpr int kNZ = 10;  // sample registers per lane: samples i + 50 t
   static constexpr int NH = 5;
   static constexpr int kWaves = 4;
-  static constexpr bool kNextTask = false;
+  static constexpr bool kExact = true;
+  static constexpr bool kFused = true;
+  static constexpr int kOcc = 4;       // fits 4 waves / SIMD (the LDS Stockham engines are register-limited to 3)
+  static constexpr int kOccStack = 4;  // as the exact Stockham engines up to N = 500
   static constexpr int kTabBins = 256;  // bins f <= 250; [255].x: the slice's non-zero flag
-  static constexpr size_t kBlockBytes = sizeof(float2) * N;     // twiddle table
-  static constexpr size_t kWaveBytes = sizeof(float2) * 2 * N;  // ping-pong buffers
-  static constexpr int kBufA = N;                               // bufB = bufA + kBufA
+  static constexpr size_t kBlockBytes = sizeof(float2) * NFFT;     // twiddle table
+  static constexpr size_t kWaveBytes = sizeof(float2) * 2 * NFFT;  // ping-pong buffers
+  static constexpr int kBufA = NFFT;                               // bufB = bufA + kBufA
   static constexpr int kPad = 6;  // 2 (100 + kPad) = 20 mod 32 dwords: the 20-dword runs of consecutive i / 10 abut
 
-  __device__ EngF500(char* lds, int wave, int lane_) : FusedOps<EngF500, kNZ, 5>(lds, wave, lane_, N) {}
-  static __device__ void block_init(char* lds) { init_twiddles<N>(reinterpret_cast<float2*>(lds)); }
+  __device__ EngF500(char* lds, int wave, int lane_) : FusedOps<EngF500, kNZ, 5>(lds, wave, lane_, NFFT) {}
+  static __device__ void block_init(char* lds) { init_twiddles<NFFT>(reinterpret_cast<float2*>(lds)); }
 
   static __device__ __forceinline__ int bin(int l, int j) {
     if (j < 3) return l <= 50 ? l + 100 * j : -1;
     return (l >= 1 && l <= 49) ? 100 - l + 100 * (j - 3) : -1;
   }
-  static __device__ __forceinline__ int slot(int n) { return n; }
 
   // stage-1 operands z[t] = (re, im)[i + 50 t], t < 10, i = min(lane, 49), of the slices starting at re / im.
   // Branch-free: lanes past the 50 stage-1 butterflies load lane 49's samples again, which stage1() does not
@@ -775,7 +794,7 @@ struct EngF500 : FusedOps<EngF500, 10, 5> {
   template <class F>
   __device__ __forceinline__ void finish_with(F&& acc) const {
     wave_sync();
-    stockham_stage_any<N, 10, 10, 0, kPad>(bufB, bufA, tw, opaque(lane));
+    stockham_stage_any<NFFT, 10, 10, 0, kPad>(bufB, bufA, tw, opaque(lane));
     wave_sync();
     const int ln = opaque(lane);  // the stage's addresses formed per call, not held in registers between calls
     if (ln <= 50) {
@@ -822,27 +841,18 @@ struct EngF500 : FusedOps<EngF500, 10, 5> {
     float2* const bufP = bufB - 4 * kPad;
     store_conj_hermitian<EngF500>(bufB, Cf, Co, lane);
     wave_sync();
-    stockham_stage_any<N, 1, 10>(bufB, bufA, tw, opaque(lane));
+    stockham_stage_any<NFFT, 1, 10>(bufB, bufA, tw, opaque(lane));
     wave_sync();
-    stockham_stage_any<N, 10, 10, 0, kPad>(bufA, bufP, tw, opaque(lane));
+    stockham_stage_any<NFFT, 10, 10, 0, kPad>(bufA, bufP, tw, opaque(lane));
     wave_sync();
-    stockham_stage_any<N, 100, 5, kPad, 0>(bufP, bufA, tw, opaque(lane));
+    stockham_stage_any<NFFT, 100, 5, kPad, 0>(bufP, bufA, tw, opaque(lane));
     wave_sync();
     return bufA;
   }
 
-  __device__ const float2* correlate(const RowTask& t, const RowTask& nt, bool has_next, int w, int hop) {
-    float2 Cf[NH], Co[NH];
-    this->spectra(t, nt, has_next, w, hop, Cf, Co);
-    return inverse(Cf, Co);
-  }
-
   __device__ float2 twiddle(int m) const { return tw[m]; }
 
-  __device__ float2 c(const float2* Y, int k, int) const {
-    const float2 v = Y[k];
-    return make_float2(v.x, -v.y);
-  }
+  __device__ float2 c(const float2* Y, int k, int w_) const { return corr_at<NFFT, !kExact>(Y, k, w_); }
 };
 
 
@@ -868,34 +878,39 @@ struct EngF500 : FusedOps<EngF500, 10, 5> {
 // conflict free; buffer B is plain.  (An XOR-swizzled radix-4 layout cut the conflicts further but cost 25 % more VALU
 // for no gain)
 struct EngP1024 : FusedOps<EngP1024, 8, 9> {
-  static constexpr int N = 1024;
   static constexpr int NFFT = 1024;
-  static constexpr int NJ = 8;  // sample registers: n < N / 2
+  static constexpr int NJ = 8;   // lags per lane in the epilogues (dvh_vsg.hip): w <= 512
+  static constexpr int kNZ = 8;  // sample registers per lane: samples lane + 64 j < NFFT / 2
   static constexpr int NH = 9;
   static constexpr int kWaves = 4;
-  static constexpr bool kNextTask = false;
+  static constexpr bool kExact = false;
+  static constexpr bool kFused = true;
+  static constexpr int kOcc = 3;  // register-limited to 3 waves / SIMD
+  // the plain stack kernel holds two accumulated side spectra besides the sub-window's (4 x 9 complex per lane)
+  // and would spill at 3 waves / SIMD
+  static constexpr int kOccStack = 2;
   static constexpr int kTabBins = 520;  // bins f <= 512; [519].x: the slice's non-zero flag
-  static constexpr int kBufA = N + N / 16;
-  static constexpr size_t kWaveBytes = sizeof(float2) * (kBufA + N);  // buffers A and B
+  static constexpr int kBufA = NFFT + NFFT / 16;
+  static constexpr size_t kWaveBytes = sizeof(float2) * (kBufA + NFFT);  // buffers A and B
   // Radix-16 stage twiddles, contiguous per stage after the main table: stage Ls holds w^k, w^4k, w^8k (w = e^(-2 pi
   // i Ls' / N), Ls' = N / (16 Ls)) for k < Ls at r16_tw(Ls) + {0, Ls, 2 Ls} + k, so that a stage's reads by lanes of
   // consecutive k are consecutive (read from the main table at stride 4 k, 16 k, 32 k they cost 1.6 bank-conflict
   // cycles per LDS instruction of the whole launch).
-  static constexpr int kR16Tw = N;
+  static constexpr int kR16Tw = NFFT;
   static constexpr int kR16TwEntries = 3 * (16 + 4 + 64);
   static constexpr int r16_tw(int Ls) { return kR16Tw + (Ls == 16 ? 0 : (Ls == 4 ? 48 : 60)); }
-  static constexpr size_t kBlockBytes = sizeof(float2) * (N + kR16TwEntries);
+  static constexpr size_t kBlockBytes = sizeof(float2) * (NFFT + kR16TwEntries);
 
-  __device__ EngP1024(char* lds, int wave, int lane_) : FusedOps<EngP1024, 8, 9>(lds, wave, lane_, N / 2) {}
+  __device__ EngP1024(char* lds, int wave, int lane_) : FusedOps<EngP1024, kNZ, 9>(lds, wave, lane_, NFFT / 2) {}
   static __device__ void block_init(char* lds) {
     float2* t = reinterpret_cast<float2*>(lds);
-    init_twiddles<N>(t);
+    init_twiddles<NFFT>(t);
     for (int e = threadIdx.x; e < kR16TwEntries; e += blockDim.x) {
       const int Ls = e < 48 ? 16 : (e < 60 ? 4 : 64), o = e - (Ls == 16 ? 0 : (Ls == 4 ? 48 : 60));
       const int j = o / Ls, k = o % Ls, mult = j == 0 ? 1 : (j == 1 ? 4 : 8);
-      const int m = mult * k * (N / (16 * Ls));
+      const int m = mult * k * (NFFT / (16 * Ls));
       double sn, cs;
-      sincospi(2.0 * (double)m / (double)N, &sn, &cs);  // init_twiddles' formula: the same float values as tw[m]
+      sincospi(2.0 * (double)m / (double)NFFT, &sn, &cs);  // init_twiddles' formula: the same float values as tw[m]
       t[kR16Tw + e] = make_float2((float)cs, (float)(-sn));
     }
   }
@@ -913,14 +928,13 @@ struct EngP1024 : FusedOps<EngP1024, 8, 9> {
       default: return l == 0 ? 512 : -1;
     }
   }
-  static __device__ __forceinline__ int slot(int n) { return n; }
 
   // z[j] = (re, im)[lane + 64 j], j < 8, zero past the sub-window (n >= w); im == nullptr: the receiver in
   // both halves (the second half's result is discarded)
-  __device__ __forceinline__ void load_ri(const float* re, const float* im, float2 (&z)[8]) const {
+  __device__ __forceinline__ void load_ri(const float* re, const float* im, float2 (&z)[kNZ]) const {
     const float* ip = im ? im : re;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < kNZ; ++j) {
       const int n = lane + 64 * j;
       z[j] = n < w ? make_float2(re[n], ip[n]) : make_float2(0.f, 0.f);
     }
@@ -936,12 +950,12 @@ struct EngP1024 : FusedOps<EngP1024, 8, 9> {
     d[(2 - o) >> 1] = sw ? make_float4(x0.x, x0.y, x1.x, x1.y) : make_float4(x2.x, x2.y, x3.x, x3.y);
   }
 
-  __device__ __forceinline__ void stage1(const float2 (&z)[8]) const {
+  __device__ __forceinline__ void stage1(const float2 (&z)[kNZ]) const {
     // radix-16 butterfly i = lane of x[i + 64 t], t < 16: the prefetched z[t] for t < 8, zero above; outputs
     // out[16 i + q] at the padded index 17 i + q (16 lanes of a store group: 16 distinct banks)
     float2 a[16];
 #pragma unroll
-    for (int t = 0; t < 8; ++t) a[t] = z[t];
+    for (int t = 0; t < kNZ; ++t) a[t] = z[t];
     dft16<true>(a);
     float2* o = bufA + 17 * lane;
 #pragma unroll
@@ -1045,24 +1059,9 @@ struct EngP1024 : FusedOps<EngP1024, 8, 9> {
     return bufB;
   }
 
-  __device__ const float2* correlate(const RowTask& t, const RowTask& nt, bool has_next, int w_, int hop) {
-    float2 Cf[NH], Co[NH];
-    this->spectra(t, nt, has_next, w_, hop, Cf, Co);
-    return inverse(Cf, Co);
-  }
-
   __device__ float2 twiddle(int m) const { return tw[m]; }
 
-  // (N * sum_s c_f[k], N * sum_s c_o[k]): the linear correlation folded to the circular one of period w
-  __device__ float2 c(const float2* Y, int k, int w_) const {
-    float2 v = Y[k];
-    if (k > 0) {
-      const float2 u = Y[N - w_ + k];
-      v.x += u.x;
-      v.y += u.y;
-    }
-    return make_float2(v.x, -v.y);
-  }
+  __device__ float2 c(const float2* Y, int k, int w_) const { return corr_at<NFFT, !kExact>(Y, k, w_); }
 };
 
 }  // namespace dvh

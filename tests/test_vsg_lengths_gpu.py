@@ -1,7 +1,7 @@
 """GPU parity of the VSG kernels at every correlation window length w the dispatch serves, against the float64
-oracle: the six engines of get_kernels (dvh_vsg.hip) at their first, last and odd w, through the per-pass gathers,
-the plain and validated class stacks, other sub-window counts, single samples at the edges of the load masks, and the
-error beyond w = 1024.
+oracle: the six engines of the engine table (engine_for, dvh_vsg.hip) at their first, last and odd w, through the
+per-pass gathers, the plain and validated class stacks, other sub-window counts, single samples at the edges of the
+load masks, and the error beyond w = 1024.
 
 Passes: synth_pass, 24 channels x 6 500 samples (610 m first channel), pivot 700, gather rows 620-780 m (19 rows: 10
 below the pivot row, 8 above), delta_t = 1.  6 500 samples, not the 5 500 of the other VSG tests: at w ~ 1000 the two
