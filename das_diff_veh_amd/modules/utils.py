@@ -5,6 +5,7 @@
   Dispersion    modules/utils.py:383-426  (same constructor, attributes, npz format, arithmetic)
   bandpass_data modules/utils.py:179-189  -> dvh_sosfiltfilt (zero-phase order-10 Butterworth)
   extract_ridge_ref_idx modules/utils.py:621-678 -> dvh_ridge (one wave per ridge)
+  win_avg_psd   modules/utils.py:715-728  -> dvh_welch_rows (one launch per window shape, das_diff_veh_amd.spectra)
   disp_curve_stats  the statistics of plot_disp_curves (:680-713), without the figure
   _cut_taper, _read_das_npz modules/utils.py:87-113 (host: the record file, its channel and taper cut; ImagingIO of
                 modules/imaging_IO.py smooths and scales the result on the device)
@@ -159,6 +160,35 @@ def extract_ridge_ref_idx(freq, vel, fv_map, ref_freq_idx=None, sigma=25, vel_ma
     out = ridges(fv, freq, vel, freq[0], np.nextafter(freq[-1], np.inf), ref_freq_idx=ref_freq_idx, sigma=sigma,
                  vel_max=vel_max, ref_vel=ref_vel)[0]
     return out
+
+
+def win_avg_psd(win_spectrum, fs, nperseg=2048):
+    """modules/utils.py:715-728: (f, Pxx_avg, Pxxs) in float64, Pxxs[i] the mean over window i's own rows of
+    scipy.signal.welch(row, fs, nperseg=nperseg) and Pxx_avg = Pxxs.mean(0).  Windows are batched by shape, one
+    float32 device batch and one dvh_welch_rows launch per shape (the rows' own spectra are never stored); ``data``
+    may be a host array or a device tensor.  As in the reference an empty list raises IndexError, windows whose
+    spectra differ in length raise ValueError, and an nperseg above the window length is clipped with SciPy's warning."""
+    from ..device import to_device_f32
+    from ..spectra import welch_plan, welch_rows
+    shapes = [tuple(w.data.shape) for w in win_spectrum]
+    if not shapes:
+        raise IndexError("list index out of range")
+    if any(len(s) != 2 or s[0] < 1 for s in shapes):
+        raise ValueError("every window's data must be [channels >= 1, samples]")
+    plans = {n_t: welch_plan(n_t, fs, nperseg) for n_t in dict.fromkeys(s[1] for s in shapes)}
+    bins = plans[shapes[0][1]].bins
+    for s in shapes:
+        if plans[s[1]].bins != bins:
+            raise ValueError(f"could not broadcast input array from shape ({plans[s[1]].bins},) into shape ({bins},)")
+    groups = {}
+    for i, s in enumerate(shapes):
+        groups.setdefault(s, []).append(i)
+    Pxxs = np.zeros((len(shapes), bins))
+    for s, idx in groups.items():
+        batch = to_device_f32([win_spectrum[i].data for i in idx])
+        _, out = welch_rows(batch, fs, plan=plans[s[1]])
+        Pxxs[idx] = out.to("cpu").numpy()
+    return plans[shapes[-1][1]].freqs, np.mean(Pxxs, axis=0), Pxxs
 
 
 def disp_curve_stats(freqs, freq_lb, freq_up, ridge_vels):

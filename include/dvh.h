@@ -364,6 +364,30 @@ int dvh_peak_likelihood(const int32_t* peaks, int32_t cap, const int32_t* count,
 int dvh_kf_track(const int32_t* peaks, int32_t cap, const int32_t* count, int32_t n_steps, const double* x_sel,
                  const int32_t* veh_base, int32_t n_veh, double sigma_a, double* veh_states, void* stream);
 
+/* ---------------------------------------------------------------- spectra (win_avg_psd, plot_psd_vs_offset)
+ * scipy.signal.welch(x, fs, nperseg, nfft=nfft) with SciPy's defaults, for float32 rows
+ * x[n_groups][rows_per_group][n_t] (group_stride, row_stride in elements; the time axis is contiguous):
+ *   noverlap = nperseg / 2, step = nperseg - noverlap, nseg = (n_t - noverlap) / step (the tail is ignored);
+ *   per segment: minus its own mean (float64), times win[nperseg] (float64, the caller's periodic Hann), rFFT of
+ *   length nfft (zero padded), re^2 + im^2; the mean over segments times scale = 1 / (fs sum win^2), every bin but
+ *   DC (and Nyquist when nfft is even) doubled.
+ * out[n_groups][nfft / 2 + 1] float64 is the mean of that over the group's rows: rows_per_group = 1 gives the rows'
+ * own spectra (a gather), rows_per_group = C the per-window spectrum of win_avg_psd (modules/utils.py:715-728)
+ * without the rows' spectra ever being stored.  A segment holding NaN or +-inf makes its group NaN in every bin.
+ *   nfft 256, 512, 1024, 2048, 4096   one wave per segment, a packed nfft / 2-point float32 transform (the window is
+ *                                     rounded to float32 with the products it forms); means and every sum over
+ *                                     segments, rows and waves in float64 in a fixed order (a value does not depend
+ *                                     on strides, alignment or n_groups); tab may be NULL
+ *   any other nfft                    direct float64 sums against tab[nfft][2] = (cos, -sin)(2 pi m / nfft); needs
+ *                                     16 nfft + 8 nperseg bytes of one block's LDS (160 KiB), else -4
+ * ws: dvh_welch_rows_workspace bytes (0 for at most 64 rows per group and for the direct form; NULL is then fine).
+ * The caller clips nperseg to n_t as SciPy does: nperseg > n_t, nfft < nperseg and an nfft neither form takes are -4,
+ * bad pointers, strides shorter than the rows and overlapping buffers -2; nothing is launched then. */
+int64_t dvh_welch_rows_workspace(int64_t n_groups, int32_t rows_per_group, int32_t nfft);
+int dvh_welch_rows(const float* x, int64_t n_groups, int64_t group_stride, int32_t rows_per_group, int64_t row_stride,
+                   int32_t n_t, const double* win, int32_t nperseg, int32_t nfft, double scale, const double* tab,
+                   double* out, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
