@@ -282,6 +282,85 @@ __global__ __launch_bounds__(256) void fk_contract_kernel(const double* __restri
   }
 }
 
+// 2b. The same contraction for tables too large for one block's LDS (more than ~128 channels, or the full
+// grid of the public fk() from 65 channels on): one block = (gather b, kFtM wavenumbers m, 32 f-bins).  It holds
+// the Re and the Im rows of its m (rows m and MT + m of A) as 2 * kFtM / 16 x 2 MFMA tiles, four per wave,
+// accumulated in registers while the channel dimension passes through LDS in chunks of kFtK rows of [Dr; Di].
+// Each element is summed over k in the order of fk_contract_kernel.
+constexpr int kFtM = 64;  // wavenumbers per block
+constexpr int kFtK = 64;  // rows of [Dr; Di] per LDS chunk
+constexpr int kFtT = 2 * (kFtM / 16) * (kFN / 16) / 4;  // MFMA tiles per wave
+
+__global__ __launch_bounds__(256) void fk_contract_tiled_kernel(const double* __restrict__ D, int32_t nch, int32_t n_fb,
+                                                                 const double* __restrict__ Atab, int32_t MT, int32_t K2,
+                                                                 int32_t n_kb, int32_t n_ft, double* __restrict__ FK,
+                                                                 const int32_t* __restrict__ slot,
+                                                                 const float* __restrict__ weight, int32_t n_slot) {
+  __shared__ double Bs[kFtK * (kFN + 1)];      // [kFtK][kFN + 1]
+  __shared__ double Cs[2 * kFtM * (kFN + 1)];  // [Re rows | Im rows][kFN + 1]
+  const int b = blockIdx.y, q0 = (blockIdx.x % n_ft) * kFN, m0 = (blockIdx.x / n_ft) * kFtM;
+  const double* Db = D + (int64_t)b * nch * 2 * n_fb;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  constexpr int n_nt = kFN / 16, n_half = (kFtM / 16) * n_nt;  // tiles of one half (Re or Im)
+  doublex4 acc[kFtT];
+  const double* arow[kFtT];
+  bool tok[kFtT];
+#pragma unroll
+  for (int i = 0; i < kFtT; ++i) {
+    acc[i] = doublex4{0.0, 0.0, 0.0, 0.0};
+    const int t = wave + 4 * i, im = t / n_half, ml = (t % n_half) / n_nt;
+    tok[i] = m0 + ml * 16 < MT;  // MT is a multiple of 16: a 16-row tile lies inside the table or outside it
+    arow[i] = Atab + (int64_t)(tok[i] ? im * MT + m0 + ml * 16 + (lane & 15) : 0) * K2;
+  }
+  for (int k0 = 0; k0 < K2; k0 += kFtK) {
+    const int kc = min(kFtK, K2 - k0);  // a multiple of 4, as K2 is
+    __syncthreads();                    // the last chunk's readers are done
+    for (int e = threadIdx.x; e < kc * kFN; e += 256) {
+      const int kk = k0 + e / kFN, n = e % kFN;
+      const int q = q0 + n;
+      double v = 0.0;
+      if (q < n_fb && kk < 2 * nch) {
+        const int x = kk < nch ? kk : kk - nch;
+        v = Db[(int64_t)x * 2 * n_fb + 2 * q + (kk < nch ? 0 : 1)];
+      }
+      Bs[(e / kFN) * (kFN + 1) + n] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kFtT; ++i) {
+      if (!tok[i]) continue;
+      const int nt = (wave + 4 * i) % n_nt;
+      for (int kk = 0; kk < kc; kk += 4) {
+        const double a = arow[i][k0 + kk + (lane >> 4)];
+        const double bb = Bs[(kk + (lane >> 4)) * (kFN + 1) + nt * 16 + (lane & 15)];
+        acc[i] = mfma_f64(a, bb, acc[i]);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kFtT; ++i) {
+    const int t = wave + 4 * i, im = t / n_half, ml = (t % n_half) / n_nt, nt = t % n_nt;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = im * kFtM + ml * 16 + (lane >> 4) + 4 * r;
+      Cs[row * (kFN + 1) + nt * 16 + (lane & 15)] = acc[i][r];  // zeros where the tile lies outside the table
+    }
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < kFtM * kFN; e += 256) {
+    const int ml = e / kFN, n = e % kFN, q = q0 + n, m = m0 + ml;
+    if (q >= n_fb || m >= n_kb) continue;
+    const double mag = hypot(Cs[ml * (kFN + 1) + n], Cs[(kFtM + ml) * (kFN + 1) + n]);
+    if (slot) {
+      const int sl = slot[b];
+      if (sl >= 0 && sl < n_slot)  // the host rejects such slots; never write outside FK
+        atomicAdd(FK + ((int64_t)sl * n_kb + m) * n_fb + q, mag * (double)weight[b]);
+    } else {
+      FK[((int64_t)b * n_kb + m) * n_fb + q] = mag;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // 3. f-v sampling + Savitzky-Golay.  One block = (gather b, 16 velocity rows), all frequencies.
 constexpr int kVC = 4;        // velocities per block: 750 blocks for one set of 3 images of 1000 x 242
@@ -1102,7 +1181,15 @@ DVH_API int dvh_disp_fk(const double* D, int32_t B, int32_t nch, int32_t n_fb, c
   if (MT % 16 || n_kb > MT || K2 < 2 * nch || K2 % 4) return set_error(-2, "invalid contraction table shape");
   if (B <= 0 || n_fb <= 0) return 0;
   const size_t lds = sizeof(double) * ((size_t)K2 * (kFN + 1) + (size_t)2 * MT * (kFN + 1));
-  if (lds > 160 * 1024) return set_error(-4, "too many channels / wavenumbers for one block");
+  // the operand and the result no longer fit one block: tile m, chunk the channels (DVH_FK_TILED=1: always, A/B)
+  const char* tiled_env = getenv("DVH_FK_TILED");
+  if (lds > 160 * 1024 || (tiled_env && atoi(tiled_env) > 0)) {
+    const int64_t n_ft = (n_fb + kFN - 1) / kFN, n_mt = (n_kb + kFtM - 1) / kFtM;
+    if (n_ft * n_mt > 0x7fffffff) return set_error(-4, "FK grid too large for one launch");
+    hipLaunchKernelGGL(fk_contract_tiled_kernel, dim3((unsigned)(n_ft * n_mt), B), dim3(256), 0, (hipStream_t)stream, D,
+                       nch, n_fb, atab, MT, K2, n_kb, (int32_t)n_ft, FK, slot, weight, n_slot);
+    return last_launch();
+  }
   if (int rc = set_dynamic_lds((const void*)fk_contract_kernel, lds)) return rc;
   dim3 grid((n_fb + kFN - 1) / kFN, B);
   hipLaunchKernelGGL(fk_contract_kernel, grid, dim3(256), lds, (hipStream_t)stream, D, nch, n_fb, atab, MT, K2, n_kb,

@@ -141,7 +141,12 @@ int dvh_disp_tdft(const float* data, int64_t b_stride, int64_t ch_stride, int32_
 
 /* Channel contraction (complex GEMM on MFMA) + |.|: FK[B][n_kb][n_fb]; with slot/weight
  * (both non-NULL) FK[slot[b]] += weight[b] * |Z_b| instead (class mean of |FK|), FK holding n_slot
- * slots (a slot outside [0, n_slot) is never written; callers validate slots on the host). */
+ * slots (a slot outside [0, n_slot) is never written; callers validate slots on the host).
+ * Any nch and n_kb: tables of up to 160 KB of LDS (8 * 33 * (K2 + 2 * MT) bytes, e.g. 128 channels x 127
+ * wavenumbers) run one block per (gather, 32 f-bins); larger ones are tiled over 64 wavenumbers per block with
+ * the channels chunked through LDS (DVH_FK_TILED=1: always, A/B), with the same sums in the same order.  What
+ * remains is the caller's dense atab (2 * MT * K2 doubles) and B <= 65535 gathers per launch.  -2 for a table
+ * shape that breaks the rules above (MT % 16, n_kb > MT, K2 < 2 * nch, K2 % 4); FK is then not written. */
 int dvh_disp_fk(const double* D, int32_t B, int32_t nch, int32_t n_fb, const double* atab, int32_t MT, int32_t K2,
                 int32_t n_kb, double* FK, const int32_t* slot, const float* weight, int32_t n_slot, void* stream);
 
