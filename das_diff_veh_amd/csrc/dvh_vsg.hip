@@ -52,27 +52,91 @@ __device__ __forceinline__ void bind_engine(E& e, const VsgArgs& A, const float2
   }
 }
 
-// One row task's cross spectra: a fused engine with a bound pivot-spectra table uses it (stack kernels).
+// The per-task state of a stack wave's pass loop.  Fused engines: the task deck (FusedOps::Deck, consumed by
+// direct_task) and the hand of passes the loop holds (FusedOps::Hand; n = 0: none, the tables are read pass by
+// pass).
+struct NoDeck {
+  int n = 0;
+};
+template <class E, bool FUSED = E::kFused>
+struct PassLoop {
+  using Deck = NoDeck;
+  using Hand = NoDeck;
+};
 template <class E>
-__device__ __forceinline__ void engine_spectra(E& eng, const VsgArgs& A, const RowTask& t, float2 (&Cf)[E::NH],
-                                               float2 (&Co)[E::NH]) {
+struct PassLoop<E, true> {
+  using Deck = typename E::Deck;
+  using Hand = typename E::Hand;
+};
+
+template <class E>
+__device__ __forceinline__ typename PassLoop<E>::Deck engine_deal(E& eng, const VsgArgs& A, const float* scales,
+                                                                   const int32_t* order, const float* weight, int b,
+                                                                   int e, int i) {
+  if constexpr (E::kFused) return eng.deal(A, scales, order, weight, b, e, i);
+  else return NoDeck{};
+}
+template <class E>
+__device__ __forceinline__ typename PassLoop<E>::Hand engine_hand(E& eng, const typename PassLoop<E>::Deck& D, int b) {
   if constexpr (E::kFused) {
-    if (eng.tab && eng.tab_usable(t.p, A.n_pass)) {
-      eng.spectra_tab(t, A.n_pass, A.hop, Cf, Co);
+    if constexpr (E::kDeckLoop) return eng.hand(D, b);
+    else return typename E::Hand{};
+  } else {
+    return NoDeck{};
+  }
+}
+
+// Pass order[q] of a task of row i whose passes end at e: its row task, factors and cross spectra.  With a hand
+// everything comes from it by readlane (a new hand is dealt when q runs past it).  Without one (other engines,
+// tasks of more than 64 passes, an engine without kDeckLoop) the tables are read here.
+template <class E>
+__device__ __forceinline__ void engine_pass(E& eng, const VsgArgs& A, const float* __restrict__ scales,
+                                            const int32_t* __restrict__ order, const float* __restrict__ weight,
+                                            typename PassLoop<E>::Hand& H, int e, int q, int i, RowTask& task,
+                                            float& sf, float& so, float& wp, float2 (&Cf)[E::NH],
+                                            float2 (&Co)[E::NH]) {
+  if constexpr (E::kFused) {
+    if (H.n && q >= H.first + H.n) H = eng.hand(eng.deal(A, scales, order, weight, q, min(e, q + E::kHand), i), q);
+    if (H.n) {
+      const int k = uni(q - H.first);
+      const uint32_t word = (uint32_t)eng.hand_i(H, E::kHWord, k);
+      task = eng.hand_task(A, H, k, word);
+      if (word & E::kDeckUsable) {
+        eng.spectra_tab(task, eng.deck_jobs(task, word), word >> E::kDeckFlag0, A.hop, Cf, Co);
+      } else {
+        eng.spectra(task, A.w, A.hop, Cf, Co);
+      }
+      sf = eng.hand_f(H, E::kHSf, k);
+      so = eng.hand_f(H, E::kHSo, k);
+      wp = eng.hand_f(H, E::kHWp, k);
       return;
     }
   }
-  eng.spectra(t, A.w, A.hop, Cf, Co);
+  const int p = sld(order + q);
+  task = make_task(A, p, i);
+  bool tabbed = false;
+  if constexpr (E::kFused) {
+    if (eng.tab && eng.tab_usable(p, A.n_pass)) {
+      const int32_t* head = tab_head<E::kTabBins>(eng.tab, A.n_pass) + (int64_t)p * kTabEnt * 2;
+      const auto J = E::tab_jobs(task, E::far_match(task.a_f, task.nwin_f, sld(head + 4), sld(head + 5)),
+                                 E::far_match(task.a_o, task.nwin_o, sld(head + 6), sld(head + 7)));
+      eng.spectra_tab(task, J, eng.tab_flags(task, J), A.hop, Cf, Co);
+      tabbed = true;
+    }
+  }
+  if (!tabbed) eng.spectra(task, A.w, A.hop, Cf, Co);
+  sf = sld(scales + 2 * p);
+  so = sld(scales + 2 * p + 1);
+  wp = sld(weight + p);
 }
 
 // A row task whose passes have only a table-served forward side, transformed across passes.  RAMP: the exact
 // engines' output-spectrum form; otherwise the forward spectrum sum (*shared: its lag convention).
 template <class E, bool RAMP>
-__device__ __forceinline__ bool engine_direct(E& eng, const VsgArgs& A, const float* scales, const int32_t* order,
-                                              const float* weight, int b, int e, int i, float2 (&Gh)[E::NH],
-                                              bool* shared = nullptr) {
+__device__ __forceinline__ bool engine_direct(E& eng, const VsgArgs& A, const typename PassLoop<E>::Deck& D,
+                                              float2 (&Gh)[E::NH], bool* shared = nullptr) {
   if constexpr (E::kFused) {
-    return eng.tab && eng.template direct_task<RAMP>(A, scales, order, weight, b, e, i, Gh, shared);
+    return eng.tab && eng.template direct_task<RAMP>(A, D, Gh, shared);
   } else {
     return false;
   }
@@ -340,13 +404,16 @@ __device__ __forceinline__ void stackf_tasks(E& eng, const VsgArgs& A, const flo
     float2 Gh[NH];
 #pragma unroll
     for (int m = 0; m < NH; ++m) Gh[m] = make_float2(0.f, 0.f);
-    const bool direct = !norm && engine_direct<E, true>(eng, A, scales, order, weight, b, e, i, Gh);
+    const auto D = engine_deal(eng, A, scales, order, weight, b, e, i);
+    const bool direct = !norm && engine_direct<E, true>(eng, A, D, Gh);
+    typename PassLoop<E>::Hand H;  // (the deck is dead once direct_task has run)
+    if (!direct) H = engine_hand(eng, D, b);
     for (int q = direct ? e : b; q < e; ++q) {
-      const int p = sld(order + q);
-      const RowTask task = make_task(A, p, i);
+      RowTask task;
       float2 Cf[NH], Co[NH];
-      engine_spectra(eng, A, task, Cf, Co);
-      const float sf = sld(scales + 2 * p), so = sld(scales + 2 * p + 1), wp = sld(weight + p);
+      float sf, so, wp;
+      engine_pass(eng, A, scales, order, weight, H, e, q, i, task, sf, so, wp, Cf, Co);
+      const int p = task.p;
       // per-pass bin / twiddle-index math recomputed here (hoisted, it only spills)
       const int lane = opaque(lane_);
       // sums of |.| over the half spectra: NaN iff some bin is NaN (sums of non-negative values never
@@ -476,24 +543,38 @@ __device__ __forceinline__ void stackp_tasks(E& eng, const VsgArgs& A, const flo
 #pragma unroll
     for (int m = 0; m < NH; ++m) Af[m] = Ao[m] = make_float2(0.f, 0.f);
     bool fs0 = false, os0 = false, any = false, anyo = false;
+    const auto D = engine_deal(eng, A, scales, order, weight, b, e, i);
     if (b < e) {
-      const RowTask t0 = make_task(A, sld(order + b), i);
-      fs0 = t0.ch <= t0.pivot;
-      os0 = t0.ch >= t0.pivot;
+      int ch0 = 0, pivot0 = 0;
+      if constexpr (E::kFused) {
+        if (D.n) {
+          ch0 = __builtin_amdgcn_readfirstlane(D.ch);
+          pivot0 = __builtin_amdgcn_readfirstlane(D.pivot);
+        }
+      }
+      if (!D.n) {
+        const int p0 = sld(order + b);
+        ch0 = sld(A.pass_tab + 2 * p0) + i;
+        pivot0 = sld(A.pass_tab + 2 * p0 + 1);
+      }
+      fs0 = ch0 <= pivot0;
+      os0 = ch0 >= pivot0;
     }
     // single-sided tasks with table-served forward slices: receivers packed across passes (fused engines)
     bool dshared = fs0;
-    const bool direct = !norm && engine_direct<E, false>(eng, A, scales, order, weight, b, e, i, Af, &dshared);
+    const bool direct = !norm && engine_direct<E, false>(eng, A, D, Af, &dshared);
     if (direct) {
       fs0 = dshared;
       any = true;
     }
+    typename PassLoop<E>::Hand H;  // (the deck is dead once direct_task has run)
+    if (!direct) H = engine_hand(eng, D, b);
     for (int q = direct ? e : b; q < e; ++q) {
-      const int p = sld(order + q);
-      const RowTask task = make_task(A, p, i);
+      RowTask task;
       float2 Cf[NH], Co[NH];
-      engine_spectra(eng, A, task, Cf, Co);
-      const float sf = sld(scales + 2 * p), so = sld(scales + 2 * p + 1), wp = sld(weight + p);
+      float sf, so, wp;
+      engine_pass(eng, A, scales, order, weight, H, e, q, i, task, sf, so, wp, Cf, Co);
+      const int p = task.p;
       const int lane = opaque(lane_);
       float af = 0.f, ao = 0.f;
 #pragma unroll

@@ -25,6 +25,7 @@
 //   NFFT       the transform length;
 //   kExact     NFFT = w (stackf_tasks), else NFFT >= 2w - 1 zero padded (stackp_tasks, the fold in corr_at());
 //   kFused     a FusedOps engine: takes the pivot-slice table and packs single-sided tasks across passes;
+//   kDeckLoop  (fused engines) the stack kernels' pass loop takes its table words from the task deck;
 //   kOcc       waves / SIMD its scales and gather kernels are compiled for;
 //   kOccStack  waves / SIMD its plain stack kernel is compiled for;
 //   kWaves     waves per block;  NJ: lags per lane in the epilogues;  NH: half-spectrum slots per lane.
@@ -431,12 +432,16 @@ struct FusedOps {
   struct TabJobs {
     int nrf, nr, ef, eo, ts, at, nt, npair;
   };
-  static __device__ __forceinline__ TabJobs tab_jobs(const RowTask& t, const int32_t* head) {
+  // a trajectory side matches its far-row entry (head words 4..7) when its slices are the same
+  static __device__ __forceinline__ bool far_match(int a, int nwin, int start, int count) {
+    return nwin > 0 && a == start && nwin == count;
+  }
+  // farf / faro: far_match() of the row's forward / other side
+  static __device__ __forceinline__ TabJobs tab_jobs(const RowTask& t, bool farf, bool faro) {
     TabJobs J;
     const bool shf = t.ch <= t.pivot, sho = t.ch >= t.pivot;
-    // a trajectory side matches its far-row entry when its slices are the same
-    const bool mf = shf || (t.nwin_f > 0 && t.a_f == sld(head + 4) && t.nwin_f == sld(head + 5));
-    const bool mo = sho || (t.nwin_o > 0 && t.a_o == sld(head + 6) && t.nwin_o == sld(head + 7));
+    const bool mf = shf || farf;
+    const bool mo = sho || faro;
     J.ef = shf ? 0 : 2;
     J.eo = sho ? 1 : 3;
     J.nrf = mf ? t.nwin_f : 0;
@@ -467,7 +472,35 @@ struct FusedOps {
     }
   }
 
-  __device__ void spectra_tab(const RowTask& t, int n_pass, int hop, float2 (&Cf)[kNH], float2 (&Co)[kNH]) {
+  // The non-zero flags of the table slices a row can use, bit side * kTabSub + q (side 0: entry ef, 1: entry
+  // eo), read from the table one by one (a task without a deck).
+  __device__ __forceinline__ uint32_t tab_flags(const RowTask& t, const TabJobs& J) const {
+    constexpr int BINS = E::kTabBins;
+    // all loads issued together (one scalar round trip); a slice the row does not use reads slice 0's flag instead
+    float v[2 * kTabSub];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+#pragma unroll
+      for (int q = 0; q < kTabSub; ++q) {
+        const bool on = q < (s == 0 ? J.nrf : J.nr - J.nrf);
+        v[s * kTabSub + q] = sld(&tab_slice<BINS>(tab, t.p, s == 0 ? J.ef : J.eo, on ? q : 0)[BINS - 1].x);
+      }
+    }
+    uint32_t fl = 0;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+#pragma unroll
+      for (int q = 0; q < kTabSub; ++q) {
+        const bool on = q < (s == 0 ? J.nrf : J.nr - J.nrf);
+        if (on && v[s * kTabSub + q] != 0.f) fl |= 1u << (s * kTabSub + q);
+      }
+    }
+    return fl;
+  }
+
+  // fl: the slices' non-zero flags (tab_flags(), or the deck's)
+  __device__ void spectra_tab(const RowTask& t, const TabJobs& J, uint32_t fl, int hop, float2 (&Cf)[kNH],
+                              float2 (&Co)[kNH]) {
     constexpr int NH_ = kNH, BINS = E::kTabBins;
 #pragma unroll
     for (int j = 0; j < NH_; ++j) {
@@ -475,8 +508,6 @@ struct FusedOps {
       Co[j] = make_float2(0.f, 0.f);
     }
     live_f = live_o = false;
-    const int32_t* head = tab_head<BINS>(tab, n_pass) + (int64_t)t.p * kTabEnt * 2;
-    const TabJobs J = tab_jobs(t, head);
     const int nj = J.npair + J.nt;
     float2 z[kNJ];
     if (nj > 0) tab_load(t, J, 0, hop, z);
@@ -498,8 +529,8 @@ struct FusedOps {
         Pa = tab_slice<BINS>(tab, t.p, s0 == 0 ? J.ef : J.eo, q0);
         Pb = tab_slice<BINS>(tab, t.p, s1 == 0 ? J.ef : J.eo, q1);
         // a receiver slice or its pivot slice identically zero: exactly zero in the reference
-        la = nzp && sld(&Pa[BINS - 1].x) != 0.f;
-        lb = (2 * k + 1 < J.nr) && nzr && sld(&Pb[BINS - 1].x) != 0.f;
+        la = nzp && ((fl >> (s0 * kTabSub + q0)) & 1u) != 0;
+        lb = (2 * k + 1 < J.nr) && nzr && ((fl >> (s1 * kTabSub + q1)) & 1u) != 0;
       }
       const bool live = pairjob ? (la || lb) : (nzp && nzr);
       if (live) self().stage1(z);
@@ -551,6 +582,143 @@ struct FusedOps {
     }
   }
 
+  // ---- The task deck: everything the passes of one (chunk, row) task need from the tables, lane k = pass
+  // order[b + k], loaded together at the start of the task (one dependent round after `order`, and the slices'
+  // non-zero flags one round later, when the row's table entries are known) and handed out by readlane:
+  // direct_task takes the whole deck, the pass loop of an engine with kDeckLoop a hand of it (below), and no
+  // table load is left in that loop or in the job loops.  A task with more than 64 passes, or a side with
+  // kDeckNwin sub-windows or more, has no deck (n = 0) and reads its tables pass by pass.
+  static constexpr int kDeckNwBits = 11, kDeckNwin = 1 << kDeckNwBits;
+  enum : uint32_t {
+    kDeckUsable = 1u << (2 * kDeckNwBits),  // tab_usable()
+    kDeckFarF = kDeckUsable << 1,           // far_match() of the forward / other side
+    kDeckFarO = kDeckUsable << 2,
+    kDeckFlag0 = 2 * kDeckNwBits + 3,       // first bit of the slices' non-zero flags (tab_flags() order)
+  };
+  struct Deck {
+    int n = 0;
+    int p = 0, ch = 0, pivot = 0, a_f = 0, a_o = 0;
+    uint32_t word = 0;  // nwin_f | nwin_o << kDeckNwBits | kDeckUsable.. | flags << kDeckFlag0
+    float sf = 0.f, so = 0.f, wp = 0.f;
+  };
+  __device__ Deck deal(const VsgArgs& A, const float* __restrict__ scales, const int32_t* __restrict__ order,
+                       const float* __restrict__ weight, int b, int e, int i) const {
+    constexpr int BINS = E::kTabBins;
+    Deck D;
+    const int n = e - b;
+    if (!tab || n < 1 || n > 64) return D;
+    const bool other = (A.flags & kFlagOtherSide) != 0;
+    const int ln = opaque(lane);  // per-task addresses formed here, not held across the task loop
+    const bool act = ln < n;
+    int row0 = 0, L = 0, Lo = 0, h1 = -1, h4 = -1, h5 = -1, h6 = -1, h7 = -1;
+    if (act) {
+      D.p = order[b + ln];
+      row0 = A.pass_tab[2 * D.p];
+      D.pivot = A.pass_tab[2 * D.p + 1];
+      const int32_t* seg = A.seg_tab + ((int64_t)D.p * A.R + i) * 4;
+      D.a_f = seg[0];
+      L = seg[1];
+      D.a_o = seg[2];
+      Lo = seg[3];
+      const int32_t* head = tab_head<BINS>(tab, A.n_pass) + (int64_t)D.p * kTabEnt * 2;
+      h1 = head[1];
+      h4 = head[4];
+      h5 = head[5];
+      h6 = head[6];
+      h7 = head[7];
+      D.sf = scales[2 * D.p];
+      D.so = scales[2 * D.p + 1];
+      D.wp = weight[D.p];
+    }
+    D.ch = row0 + i;
+    const int nwf = n_subwin(L, A.w, A.hop), nwo = other ? n_subwin(Lo, A.w, A.hop) : 0;
+    if (__ballot(nwf >= kDeckNwin || nwo >= kDeckNwin) != 0) return D;
+    const bool usable = act && h1 >= 0;
+    uint32_t word = (uint32_t)nwf | (uint32_t)nwo << kDeckNwBits;
+    if (usable) {
+      word |= kDeckUsable;
+      if (far_match(D.a_f, nwf, h4, h5)) word |= kDeckFarF;
+      if (far_match(D.a_o, nwo, h6, h7)) word |= kDeckFarO;
+      // a usable pass's table holds kTabSub slices per entry (absent ones zero, flag 0)
+      const float2* Pf = tab_slice<BINS>(tab, D.p, D.ch <= D.pivot ? 0 : 2, 0);
+      const float2* Po = tab_slice<BINS>(tab, D.p, D.ch >= D.pivot ? 1 : 3, 0);
+      float ff[kTabSub], fo[kTabSub];
+#pragma unroll
+      for (int q = 0; q < kTabSub; ++q) {
+        ff[q] = Pf[q * BINS + BINS - 1].x;
+        fo[q] = Po[q * BINS + BINS - 1].x;
+      }
+#pragma unroll
+      for (int q = 0; q < kTabSub; ++q) {
+        if (ff[q] != 0.f) word |= 1u << (kDeckFlag0 + q);
+        if (fo[q] != 0.f) word |= 1u << (kDeckFlag0 + kTabSub + q);
+      }
+    }
+    D.word = word;
+    D.n = n;
+    return D;
+  }
+  // A hand: kHand passes of a deck, kHandPer fields to a register (field f of pass k in lane kHand (f % kHandPer)
+  // + k of register f / kHandPer), which is what the pass loop holds: two registers instead of the deck's nine
+  // (the deck itself lives only from deal() to direct_task()).  A task with more passes deals a new hand every
+  // kHand passes.
+  static constexpr int kHand = 8, kHandPer = 64 / kHand;  // passes of a hand, fields to a register
+  enum { kHP, kHCh, kHPivot, kHWord, kHAf, kHAo, kHSf, kHSo, kHWp, kHFields };
+  struct Hand {
+    int n = 0;  // passes held; 0: none
+    int first = 0;  // index into `order` of pass 0
+    int v[(kHFields + kHandPer - 1) / kHandPer] = {};
+  };
+  __device__ Hand hand(const Deck& D, int first) const {
+    Hand H;
+    if (D.n == 0) return H;
+    const int ln = opaque(lane);
+    const int src = ln & (kHand - 1), grp = ln / kHand;
+    const int f[kHFields] = {D.p, D.ch, D.pivot, (int)D.word, D.a_f, D.a_o, __builtin_bit_cast(int, D.sf),
+                             __builtin_bit_cast(int, D.so), __builtin_bit_cast(int, D.wp)};
+#pragma unroll
+    for (int r = 0; r < (kHFields + kHandPer - 1) / kHandPer; ++r) {
+      int v = 0;
+#pragma unroll
+      for (int g = 0; g < kHandPer; ++g) {
+        if (kHandPer * r + g < kHFields) {
+          const int x = __shfl(f[kHandPer * r + g], src);
+          v = grp == g ? x : v;
+        }
+      }
+      H.v[r] = v;
+    }
+    H.n = min(D.n, kHand);
+    H.first = first;
+    return H;
+  }
+  // field f of pass k of the hand (wave-uniform)
+  __device__ __forceinline__ int hand_i(const Hand& H, int f, int k) const {
+    return __builtin_amdgcn_readlane(H.v[f / kHandPer], (f % kHandPer) * kHand + k);
+  }
+  __device__ __forceinline__ float hand_f(const Hand& H, int f, int k) const {
+    return __builtin_bit_cast(float, hand_i(H, f, k));
+  }
+  // pass k's row task (make_task's values); word: its kHWord
+  __device__ __forceinline__ RowTask hand_task(const VsgArgs& A, const Hand& H, int k, uint32_t word) const {
+    RowTask t;
+    t.p = hand_i(H, kHP, k);
+    t.ch = hand_i(H, kHCh, k);
+    t.pivot = hand_i(H, kHPivot, k);
+    t.row0 = 0;
+    const float* base = A.win + (int64_t)t.p * A.pass_stride;
+    t.piv = base + (int64_t)t.pivot * A.ch_stride;
+    t.rcv = base + (int64_t)t.ch * A.ch_stride;
+    t.a_f = hand_i(H, kHAf, k);
+    t.a_o = hand_i(H, kHAo, k);
+    t.nwin_f = (int)(word & (kDeckNwin - 1));
+    t.nwin_o = (int)((word >> kDeckNwBits) & (kDeckNwin - 1));
+    return t;
+  }
+  __device__ __forceinline__ TabJobs deck_jobs(const RowTask& t, uint32_t word) const {
+    return tab_jobs(t, (word & kDeckFarF) != 0, (word & kDeckFarO) != 0);
+  }
+
   // ---- direct_task: a row task whose passes have only a table-served forward side ----
   // (no row norm; every pass's other side empty, its forward slices in the table, the same sub-window count
   // W and shared/far-window kind on every pass, finite factors).  The passes' receivers are then packed two
@@ -561,62 +729,47 @@ struct FusedOps {
   // spectrum, and *shared = the passes' common lag convention.  On the configs[2] geometry these are the
   // rows below the pivot (3 receivers per pass).  Returns false (nothing done) when the task does not qualify.
   template <bool RAMP>
-  __device__ bool direct_task(const VsgArgs& A, const float* __restrict__ scales, const int32_t* __restrict__ order,
-                              const float* __restrict__ weight, int b, int e, int i, float2 (&Gh)[kNH],
-                              bool* shared = nullptr) {
+  __device__ bool direct_task(const VsgArgs& A, const Deck& D, float2 (&Gh)[kNH], bool* shared = nullptr) {
     constexpr int NH_ = kNH, BINS = E::kTabBins;
-    const int n = e - b;
-    if (n <= 1 || n > 64) return false;
-    const bool other = (A.flags & kFlagOtherSide) != 0;
-    // lane k < n: pass order[b + k] (the passes' table entries in flight together: one load latency)
+    const int n = D.n;
+    if (n <= 1) return false;
+    // lane k < n: pass order[b + k], from the task deck
     const bool act = lane < n;
-    int p = 0, row0 = 0, piv = 0, a = 0, L = 0, Lo = 0, h1 = 0, h4 = -1, h5 = -1;
-    float sf = 0.f, wp = 0.f;
-    if (act) {
-      p = order[b + lane];
-      row0 = A.pass_tab[2 * p];
-      piv = A.pass_tab[2 * p + 1];
-      const int32_t* seg = A.seg_tab + ((int64_t)p * A.R + i) * 4;
-      a = seg[0];
-      L = seg[1];
-      Lo = seg[3];
-      const int32_t* head = tab_head<BINS>(tab, A.n_pass) + (int64_t)p * kTabEnt * 2;
-      h1 = head[1];
-      h4 = head[4];
-      h5 = head[5];
-      sf = scales[2 * p];
-      wp = weight[p];
-    }
-    const int ch = row0 + i;
-    const int nwf = n_subwin(L, A.w, A.hop), nwo = other ? n_subwin(Lo, A.w, A.hop) : 0;
-    const bool shf = ch <= piv;
+    const int p = D.p, ch = D.ch, a = D.a_f;
+    const int nwf = (int)(D.word & (kDeckNwin - 1)), nwo = (int)((D.word >> kDeckNwBits) & (kDeckNwin - 1));
+    const bool shf = ch <= D.pivot;
     const int W = uni(nwf);
     const bool shf0 = uni(shf ? 1 : 0) != 0;
-    const bool mf = shf || (nwf > 0 && a == h4 && nwf == h5);
+    const bool mf = shf || (D.word & kDeckFarF) != 0;
     // the epilogue's forward factor: ff = 1 / nwin_f, times the scale (side_scale), times the class weight
     float wgt = 0.f;
     if (W > 0) {
       float ff = 1.0f / (float)W;
-      ff *= sf;
-      wgt = wp * ff;
+      ff *= D.sf;
+      wgt = D.wp * ff;
     }
-    const bool good = !act || (h1 >= 0 && nwo == 0 && nwf == W && shf == shf0 && mf && isfinite(wgt));
+    const bool good = !act || ((D.word & kDeckUsable) != 0 && nwo == 0 && nwf == W && shf == shf0 && mf && isfinite(wgt));
     if (__ballot(!good) != 0) return false;
     if (shared) *shared = shf0;
     if (W == 0) return true;  // no sub-windows on any pass: the row adds nothing
     // per-pass sources in lane k: receiver slice and table slice of sub-window 0, factor
     const uint64_t rp = reinterpret_cast<uint64_t>(A.win + (int64_t)p * A.pass_stride + (int64_t)ch * A.ch_stride + a);
     const uint64_t pp = reinterpret_cast<uint64_t>(tab_slice<BINS>(tab, p, shf ? 0 : 2, 0));
-    const uint32_t rlo = (uint32_t)rp, rhi = (uint32_t)(rp >> 32), plo = (uint32_t)pp, phi = (uint32_t)(pp >> 32);
+    // (the slices' non-zero flags ride in the low bits of the 8-byte aligned table pointer: no register of their own)
+    static_assert(kTabSub <= 3, "flag bits in the low bits of a float2 pointer");
+    const uint32_t rlo = (uint32_t)rp, rhi = (uint32_t)(rp >> 32), phi = (uint32_t)(pp >> 32);
+    const uint32_t plo = (uint32_t)pp | ((D.word >> kDeckFlag0) & ((1u << kTabSub) - 1));
     const uint32_t wv = __builtin_bit_cast(uint32_t, wgt);
     // halves in order: pass k, sub-window s (cursor of the next half to hand out)
     int hk = 0, hs = 0;
-    auto take = [&](const float*& r, const float2*& P, float& wt) {
+    auto take = [&](const float*& r, const float2*& P, float& wt, bool& nz) {
       const int k = hk;
       r = reinterpret_cast<const float*>(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)rhi, k) << 32) |
                                          (uint32_t)__builtin_amdgcn_readlane((int)rlo, k)) + hs * A.hop;
+      const uint32_t pl = (uint32_t)__builtin_amdgcn_readlane((int)plo, k);
+      nz = ((pl >> hs) & 1u) != 0;  // the pivot slice's non-zero flag
       P = reinterpret_cast<const float2*>(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)phi, k) << 32) |
-                                          (uint32_t)__builtin_amdgcn_readlane((int)plo, k)) + hs * BINS;
+                                          (pl & ~7u)) + hs * BINS;
       wt = __builtin_bit_cast(float, __builtin_amdgcn_readlane((int)wv, k));
       if (++hs == W) {
         hs = 0;
@@ -630,9 +783,10 @@ struct FusedOps {
     const float *ra, *rb;
     const float2 *Pa, *Pb;
     float wa, wb = 0.f;
-    take(ra, Pa, wa);
+    bool fa, fb = false;
+    take(ra, Pa, wa, fa);
     bool hb = hk < n;
-    if (hb) take(rb, Pb, wb);
+    if (hb) take(rb, Pb, wb, fb);
     else {
       rb = ra;
       Pb = Pa;
@@ -647,8 +801,8 @@ struct FusedOps {
         br = maxbits(br, z[j].y);
       }
       // a receiver slice or its pivot slice identically zero: exactly zero in the reference
-      const bool la = (__ballot(bp != 0) != 0) && sld(&Pa[BINS - 1].x) != 0.f;
-      const bool lb = hb && (__ballot(br != 0) != 0) && sld(&Pb[BINS - 1].x) != 0.f;
+      const bool la = (__ballot(bp != 0) != 0) && fa;
+      const bool lb = hb && (__ballot(br != 0) != 0) && fb;
       const bool live = la || lb;
       if (live) self().stage1(z);
       else check_untransformed(z, __builtin_amdgcn_readlane(p, (2 * jb) / W),
@@ -656,9 +810,9 @@ struct FusedOps {
       const float2 *Pa_c = Pa, *Pb_c = Pb;
       const float wa_c = wa, wb_c = wb;
       if (jb + 1 < nj) {  // the next pair's samples, loaded under this transform
-        take(ra, Pa, wa);
+        take(ra, Pa, wa, fa);
         hb = hk < n;
-        if (hb) take(rb, Pb, wb);
+        if (hb) take(rb, Pb, wb, fb);
         else {
           rb = ra;
           Pb = Pa;
@@ -744,6 +898,7 @@ struct EngF500 : FusedOps<EngF500, 10, 5> {
   static constexpr int kWaves = 4;
   static constexpr bool kExact = true;
   static constexpr bool kFused = true;
+  static constexpr bool kDeckLoop = true;
   static constexpr int kOcc = 4;       // fits 4 waves / SIMD (the LDS Stockham engines are register-limited to 3)
   static constexpr int kOccStack = 4;  // as the exact Stockham engines up to N = 500
   static constexpr int kTabBins = 256;  // bins f <= 250; [255].x: the slice's non-zero flag
@@ -885,6 +1040,8 @@ struct EngP1024 : FusedOps<EngP1024, 8, 9> {
   static constexpr int kWaves = 4;
   static constexpr bool kExact = false;
   static constexpr bool kFused = true;
+  // its stack kernels sit at the 256-register limit of 2 waves / SIMD: a hand in the pass loop spills (20 B)
+  static constexpr bool kDeckLoop = false;
   static constexpr int kOcc = 3;  // register-limited to 3 waves / SIMD
   // the plain stack kernel holds two accumulated side spectra besides the sub-window's (4 x 9 complex per lane)
   // and would spill at 3 waves / SIMD
