@@ -80,13 +80,16 @@ __device__ __forceinline__ double sosm_mq(const double* __restrict__ mats, bool 
 }
 
 // Lanes e < NST: unit state e_e, zero input (Hm[:, e], M[:, e]); lane NST: zero state, unit sample (h, g).  Then
-// Mzi = M zi, MQ = M^Q and MQ16 = M^Q16 by repeated products (threads (row, col) of the 20 x 20 result, LDS): the
+// Mzi = M zi, MQ = M^Q and MQ16 = M^Q16 by repeated products (threads (row, col) of the NST x NST result, LDS): the
 // group transitions of the 8-group scans (sosm_scan_kernel, sosm_scanr_kernel) and the 16-group one (sosm_scanm).
+// One thread per element of the products: 512 threads up to 11 sections (22 x 22), 1 024 above (32 x 32 at 16).
+__host__ __device__ constexpr int sosm_mats_threads(int ns) { return 4 * ns * ns <= 512 ? 512 : 1024; }
 template <int NS>
-__global__ __launch_bounds__(512) void sosm_mats_kernel(const double* __restrict__ sos, const double* __restrict__ zi,
+__global__ __launch_bounds__(sosm_mats_threads(NS)) void sosm_mats_kernel(const double* __restrict__ sos, const double* __restrict__ zi,
                                                         int32_t Q, int32_t Q16, double* __restrict__ mats) {
   using O = SosmMats<NS>;
   constexpr int NST = 2 * NS;
+  static_assert(NST * NST <= sosm_mats_threads(NS), "one thread per element of the NST x NST products");
   __shared__ double P[NST * NST], R[NST * NST], M0[NST * NST];
   const int e = threadIdx.x;
   if (e <= NST) {
@@ -177,14 +180,17 @@ __device__ __forceinline__ double sosm_ext(const T* __restrict__ x, const SosGeo
 // (k index = sample 4 kk + q, or state KS q + q'):
 //   hq[q][64 + d] = h[d] (0 for d < 0) and hr[q][64 + d] = h[-d], one copy per lane group q at stride 145: the
 //     Toeplitz factors T[i][j] = h[i - j] = hq[q][64 + i - j] and U[i][j] = h[j - i] = hr[q][64 + i - j]
-//   hm[i][m] = Hm[i][m], stride 21;  ga[j][m] = g[L - 1 - j][m], stride 48;  gb[m][i] = g[i][m], stride 66
-//   (rows m >= 2 NS zero)
-constexpr int kHq = 145, kHmLd = 21, kGaLd = 33, kGbLd = kSmLd;
+//   hm[i][m] = Hm[i][m], stride sosm_hm_ld: the 4 KS state slots a row is read at (KS = ceil(2 NS / 4) per lane
+//     group; slots m >= 2 NS zero) and odd, 21 up to 10 sections, 33 at 16
+//   ga[j][m] = g[L - 1 - j][m], stride 33;  gb[m][i] = g[i][m], stride 65  (rows m >= 2 NS zero)
+constexpr int kHq = 145, kGaLd = 33, kGbLd = kSmLd;
+__host__ __device__ constexpr int sosm_hm_ld(int nst) { return nst <= 20 ? 21 : (4 * ((nst + 3) / 4)) | 1; }
 template <int NS>
 __device__ __forceinline__ void sosm_tables(const double* __restrict__ mats, double* hq, double* hr, double* hm, double* ga,
                                             double* gb) {
   using O = SosmMats<NS>;
-  constexpr int NST = 2 * NS;
+  constexpr int NST = 2 * NS, kHmLd = sosm_hm_ld(NST);
+  static_assert(kHmLd >= 4 * ((NST + 3) / 4) && NST <= kSmRows && NST < kGaLd, "operator tables narrower than the state");
   for (int v = threadIdx.x; v < 4 * kHq; v += blockDim.x) {
     const int d = v % kHq - kSmL;
     if (hq) hq[v] = (d >= 0 && d < kSmL) ? mats[O::h + d] : 0.0;
@@ -441,7 +447,7 @@ template <typename T, int NS>
 __global__ __launch_bounds__(256) void sosm_fc_kernel(const T* __restrict__ x, SosGeom G, const double* __restrict__ mats,
                                                       const double* __restrict__ zi, const double* __restrict__ Sf,
                                                       double* __restrict__ y, double* __restrict__ Sb) {
-  constexpr int NST = 2 * NS, KS = (NST + 3) / 4;
+  constexpr int NST = 2 * NS, KS = (NST + 3) / 4, kHmLd = sosm_hm_ld(NST);
   __shared__ double hq[4 * kHq], hm[kSmL * kHmLd], gb[kSmRows * kGbLd], imgs[4][16 * kSmLd];
   sosm_tables<NS>(mats, hq, nullptr, hm, nullptr, gb);
   __syncthreads();
@@ -613,7 +619,7 @@ __global__ __launch_bounds__(64) void sosm_bf_kernel(T* __restrict__ x, SosGeom 
 template <typename T, int NS>
 __global__ __launch_bounds__(256, kSmOcc) void sosm_bc_kernel(T* __restrict__ x, SosGeom G, const double* __restrict__ mats,
                                                       const double* __restrict__ y, const double* __restrict__ Sb) {
-  constexpr int NST = 2 * NS, KS = (NST + 3) / 4;
+  constexpr int NST = 2 * NS, KS = (NST + 3) / 4, kHmLd = sosm_hm_ld(NST);
   __shared__ double hr[4 * kHq], hm[kSmL * kHmLd], imgs[4][16 * kSmLd];
   sosm_tables<NS>(mats, nullptr, hr, hm, nullptr, nullptr);
   __syncthreads();
@@ -1061,7 +1067,7 @@ bool sosm_fits(const SosGeom& G) { return G.n_rows * (int64_t)G.nb < (1LL << 31)
 
 template <int NS>
 static void sosm_plan(const double* sos, const double* zi, const SosGeom& G, double* plan, hipStream_t st) {
-  hipLaunchKernelGGL(sosm_mats_kernel<NS>, dim3(1), dim3(512), 0, st, sos, zi, (int32_t)sosm_scan_q(G.nb),
+  hipLaunchKernelGGL(sosm_mats_kernel<NS>, dim3(1), dim3(sosm_mats_threads(NS)), 0, st, sos, zi, (int32_t)sosm_scan_q(G.nb),
                      (int32_t)sosm_scan_q16(G.nb), plan);
 }
 

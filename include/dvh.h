@@ -210,7 +210,9 @@ int dvh_ridge(const float* fv, int64_t b_stride, int32_t B, int32_t nV, int32_t 
  * dtype: 0 float32, 1 float64; data modified in place. */
 
 /* scipy.signal.sosfiltfilt(sos, x, axis=-1) per row (bandpass_data, modules/utils.py:179-189);
- * zi = sosfilt_zi(sos) [n_sec][2] (device); n_sec <= 16.  Time-parallel: each row is filtered in blocks
+ * zi = sosfilt_zi(sos) [n_sec][2] (device).  Any cascade of 1 <= n_sec <= 16 sections (else -4), in both forms; a
+ * section may be first-order (b2 = a2 = 0: odd-order low-pass and high-pass designs), with SciPy's padlen for it.
+ * n_t > padlen (else -4, x untouched).  Time-parallel: each row is filtered in blocks
  * (zero-state block filters, a scan of the 2 n_sec block states, re-filter), forward then backward, the blocks by
  * the filter's own recursion (any stable design).  work: 16-byte aligned device buffer of
  * dvh_sosfiltfilt_workspace(n_rows, n_t, n_sec, padlen) bytes. */

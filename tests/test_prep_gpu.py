@@ -131,25 +131,10 @@ def test_matrix_form_record_lengths(device, n_rows, n_t):
 
 
 def _planned_run(device, sos, host, plan_n_t):
-    """dvh_sosfiltfilt_plan for a record of plan_n_t samples, then dvh_sosfiltfilt_planned on host's rows."""
-    import scipy.signal
-    import torch
-
-    from das_diff_veh_amd import _lib
-    from das_diff_veh_amd.preprocess import _padlen
-    n_rows, n_t = host.shape
-    padlen = _padlen(sos)
-    sos_t = torch.from_numpy(np.ascontiguousarray(sos, dtype=np.float64)).to(device)
-    zi_t = torch.from_numpy(np.ascontiguousarray(scipy.signal.sosfilt_zi(sos), dtype=np.float64)).to(device)
-    dev = torch.from_numpy(host.copy()).to(device)
-    nbytes = int(_lib.load().dvh_sosfiltfilt_workspace(n_rows, n_t, len(sos), padlen))
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-    plan = torch.empty(int(_lib.load().dvh_sosfiltfilt_plan_bytes(len(sos))) // 8, dtype=torch.float64, device=device)
-    _lib.call("dvh_sosfiltfilt_plan", _lib.ptr(sos_t), len(sos), _lib.ptr(zi_t), plan_n_t, padlen, _lib.ptr(plan),
-              _lib.stream_of(device))
-    _lib.call("dvh_sosfiltfilt_planned", _lib.ptr(dev), 1, n_rows, dev.stride(0), n_t, _lib.ptr(sos_t), len(sos),
-              padlen, _lib.ptr(zi_t), _lib.ptr(plan), _lib.ptr(work), _lib.stream_of(device))
-    return dev.cpu().numpy()
+    """dvh_sosfiltfilt_plan for a record of plan_n_t samples, then dvh_sosfiltfilt_planned on host's rows
+    (tests/sos_cases.py run_filtfilt: any dtype, row stride and form)."""
+    from tests.sos_cases import run_filtfilt
+    return run_filtfilt(device, sos, host, "matrix", plan_n_t=plan_n_t)
 
 
 def test_matrix_form_low_order_lds_resident_scan(device):
