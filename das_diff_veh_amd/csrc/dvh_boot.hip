@@ -18,15 +18,17 @@
 namespace dvh {
 
 // out[b][k] = (sum_{j < m} G[sel[b][j]][k]) / m over the contiguous K-element block of each pass,
-// summed in selection order (the reference's sum(images) / len(images)).  float4 per lane; the loads of 8
-// selections are issued before their adds (in order), so a lane keeps 8 gathers' reads in flight.
+// summed in selection order (the reference's sum(images) / len(images); sum() takes the first image as it is,
+// VirtualShotGather.__radd__, so the accumulator starts at -0: a +0 start would turn a -0 of it into +0).
+// float4 per lane; the loads of 8 selections are issued before their adds (in order), so a lane keeps 8 gathers'
+// reads in flight.
 __device__ __forceinline__ void select_mean_one(const float* __restrict__ G, int64_t pass_stride, int64_t K,
                                                 const int32_t* __restrict__ s, int32_t m, float* __restrict__ o,
                                                 bool vec) {
   if (vec) {
     const int64_t k4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (4 * k4 >= K) return;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 acc = make_float4(-0.f, -0.f, -0.f, -0.f);  // -0 + x == x for every x: the sum starts AT the first pass
     int j = 0;
     for (; j + 8 <= m; j += 8) {
       float4 g[8];
@@ -51,7 +53,7 @@ __device__ __forceinline__ void select_mean_one(const float* __restrict__ G, int
     reinterpret_cast<float4*>(o)[k4] = make_float4(acc.x / (float)m, acc.y / (float)m, acc.z / (float)m, acc.w / (float)m);
   } else {
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < K; k += (int64_t)gridDim.x * blockDim.x) {
-      float acc = 0.f;
+      float acc = -0.f;
       for (int j = 0; j < m; ++j) acc += G[(int64_t)s[j] * pass_stride + k];
       o[k] = acc / (float)m;
     }
@@ -233,7 +235,10 @@ __global__ __launch_bounds__(64) void ridge_kernel(const float* __restrict__ fv,
     }
     for (int i = 0; i < nb; ++i) {
       const int r = column_argmax(F, nF, c0 + i, bi, nV, lane);
-      if (lane == 0) o[i] = r >= 0 ? vel[r] : NAN;
+      if (lane == 0) {
+        o[i] = r >= 0 ? vel[r] : NAN;
+        if (picks) picks[(int64_t)b * nb + i] = o[i];  // nothing is smoothed here: the raw picks are the result
+      }
       err |= r < 0;
     }
     if (lane == 0) status[b] = err;

@@ -185,7 +185,8 @@ int dvh_disp_fv_mfma(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, co
  * stack, its f-v image (dvh_disp_*) and the ridge picks (extract_ridge_ref_idx, modules/utils.py:621-678). */
 
 /* out[b][k] = (sum_{j < m} G[sel[b * m + j] * pass_stride + k]) / m for k < K, summed in selection
- * order (sum(images) / len(images), apis/imaging_classes.py:106-107). */
+ * order (sum(images) / len(images), apis/imaging_classes.py:106-107).  The sum starts at the first selected pass, as
+ * sum() does: a selection of one pass returns it bit for bit, -0.0 included. */
 int dvh_select_mean(const float* G, int64_t pass_stride, int64_t K, const int32_t* sel, int32_t B, int32_t m,
                     float* out, int64_t out_stride, void* stream);
 
@@ -201,7 +202,8 @@ int dvh_select_mean_var(const float* G, int64_t pass_stride, int64_t K, const in
  * (column nb + ref, then the reference's loop order: forward to the end, then 0 .. nb - 1 again).  Picks of the last two modes are
  * smoothed by savgol(sgl, 2) given as sg = {h[sgl], left[sgl/2][sgl], right[sgl/2][sgl]}.
  * out[B][nb] float64; status[b] = 1 when a window held no velocity (the reference raises); picks
- * (nullable, [B][nb] float64) receives the raw picks before the smoothing. */
+ * (nullable, [B][nb] float64) receives the raw picks before the smoothing; in vel_max mode, where nothing is
+ * smoothed, the kernel writes picks[b][i] = out[b][i]. */
 int dvh_ridge(const float* fv, int64_t b_stride, int32_t B, int32_t nV, int32_t nF, int32_t c0, int32_t nb,
               const double* vel, int32_t ref, double sigma, double vel_max, const double* vref, const double* sg,
               int32_t sgl, double* out, int32_t* status, double* picks, void* stream);

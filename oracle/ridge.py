@@ -18,9 +18,10 @@ from . import vsg as ovsg
 
 
 def extract_ridge_ref_idx(freq, vel, fv_map, ref_freq_idx=None, sigma=25, vel_max=400, ref_vel=None,
-                          return_picks=False):
+                          return_picks=False, window_length=25):
     """modules/utils.py:621-678: vel ascending (reversed to the map's row order), fv_map [Nvel, Nfreq].
-    return_picks=True also returns the raw picks before savgol (the walk's per-column argmax)."""
+    return_picks=True also returns the raw picks before savgol (the walk's per-column argmax).  window_length is
+    the savgol window (the reference's fixed 25; the C ABI's sgl takes others)."""
     vel = vel[::-1]
     if ref_freq_idx is None:
         max_idx = np.abs(vel_max - vel).argmin()
@@ -37,7 +38,7 @@ def extract_ridge_ref_idx(freq, vel, fv_map, ref_freq_idx=None, sigma=25, vel_ma
         for i in range(len(freq)):
             mask = (vel > vr[i] - sigma) & (vel < vr[i] + sigma)
             out[i] = vel[mask][np.argmax(fv_map[mask, i])]
-    sm = scipy.signal.savgol_filter(out, 25, 2)
+    sm = scipy.signal.savgol_filter(out, window_length, 2)
     return (sm, out) if return_picks else sm
 
 
