@@ -147,8 +147,9 @@ class VirtualShotGather:
         np.savez(os.path.join(fdir, fname), XCF_out=self.XCF_out, x_axis=self.x_axis, t_axis=self.t_axis, **kwargs)
 
     def compute_disp_image(self, freqs=np.arange(0.8, 25, 0.1), vels=np.arange(200, 1200), norm=False,
-                           start_x=None, end_x=None):
-        """apis/virtual_shot_gather.py:247-258: nearest-offset channel slice -> Dispersion(dx=8.16)."""
+                           start_x=None, end_x=None, transform="fk"):
+        """apis/virtual_shot_gather.py:247-258: nearest-offset channel slice -> Dispersion(dx=8.16).
+        ``transform`` is Dispersion's: "fk" (map_fv) or "slant" (the phase-shift transform on the sliced rows)."""
         from ..modules.utils import Dispersion
         if start_x is None:
             start_x = self.x_axis[0]
@@ -157,7 +158,7 @@ class VirtualShotGather:
         s = np.abs(self.x_axis - start_x).argmin()
         e = np.abs(self.x_axis - end_x).argmin()
         self.disp = Dispersion(self.XCF_out[s:e + 1], 8.16, self.t_axis[1] - self.t_axis[0], freqs=freqs, vels=vels,
-                               norm=norm)
+                               norm=norm, transform=transform)
 
     def save_disp_to_npz(self, *args, **kwargs):
         assert self.disp, "please run obj.compute_disp_image() first"

@@ -316,3 +316,130 @@ def fv_class_means(data, plan: DispPlan, slots, n_slot, norm=False, counts=None)
     counts = np.bincount(slots, minlength=n_slot) if counts is None else np.asarray(counts)
     w = np.where(counts[slots] > 0, 1.0 / np.maximum(counts[slots], 1), 0.0)
     return fv_from_fk(fk_grid(data, plan, norm=norm, slots=slots, weights=w, n_slot=n_slot), plan)
+
+
+# ---------------------------------------------------------------------------------------------
+# Phase-shift (frequency-domain slant-stack) transform: map_fv_FD_slant_stack, modules/utils.py:429-454
+
+
+class SlantPlan:
+    """Host tables of the phase-shift transform for one (nch, nt, dx, dt, freqs, vels, rows) geometry, with the
+    reference's own expressions:
+      nf = 2 ** (1 + ceil(log(nt, 2))), f_idx = argmin |f - fftfreq(nf, dt)| per frequency        :437-451
+    ``bins`` are the sorted unique f_idx (DFT bin numbers), ``fb`` each frequency's position among them, ``wt`` the
+    time-DFT twiddles of those bins in dvh_disp_tdft's layout, and rows [row0, row0 + n_row) the gather rows
+    ``rows`` = (start, stop) slices out of nch (the reference's data[6:25])."""
+
+    def __init__(self, nch, nt, dx, dt, freqs, vels, rows=(6, 25)):
+        self.nch, self.nt, self.dx, self.dt = int(nch), int(nt), float(dx), float(dt)
+        self.freqs = np.ascontiguousarray(np.asarray(freqs, dtype=np.float64).ravel())
+        self.vels = np.ascontiguousarray(np.asarray(vels, dtype=np.float64).ravel())
+        self.nF, self.nV = self.freqs.size, self.vels.size
+        if not np.isfinite(self.vels).all() or (self.vels == 0).any():
+            raise ValueError("math domain error: every velocity must be finite and non-zero")
+        start, stop, _ = slice(*rows).indices(self.nch)
+        self.row0, self.n_row = start, max(0, stop - start)
+        self.nf = nf = 2 ** (1 + math.ceil(math.log(self.nt, 2)))
+        fft_freqs = np.fft.fftfreq(nf, d=self.dt)
+        self.fidx = np.array([np.abs(f - fft_freqs).argmin() for f in self.freqs], dtype=np.int64)
+        self.bins = np.unique(self.fidx)
+        self.n_fb = self.bins.size
+        self.fb = np.searchsorted(self.bins, self.fidx).astype(np.int32)
+        ang = 2.0 * np.pi * ((np.outer(np.arange(self.nt), self.bins) % nf) / nf)
+        wt = np.empty((self.nt, 2 * self.n_fb))
+        wt[:, 0::2] = np.cos(ang)
+        wt[:, 1::2] = -np.sin(ang)
+        self.wt = wt
+        self._dev = {}
+
+    def tables(self, device):
+        key = str(device)
+        if key not in self._dev:
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+            self._dev[key] = dict(wt=t(self.wt), fb=t(self.fb), freqs=t(self.freqs), vels=t(self.vels))
+        return self._dev[key]
+
+
+def _slant_spectra(data, plan: SlantPlan, norm):
+    """dvh_disp_tdft of the plan's rows at the plan's bins: D [B * n_row, 2 * n_fb] float64 (with ``norm`` of the rows
+    divided by their L1 norm), or None when the transform has no rows or no frequencies."""
+    _check(data, plan)
+    if plan.n_row == 0 or plan.n_fb == 0:
+        return None
+    dev, B = data.device, data.shape[0]
+    st = _lib.stream_of(dev)
+    rows = data[:, plan.row0:plan.row0 + plan.n_row]
+    scale = None
+    if norm:
+        scale = torch.empty(B * plan.n_row, dtype=torch.float32, device=dev)
+        _lib.call("dvh_disp_row_l1", _lib.ptr(rows), rows.stride(0), rows.stride(1), B, plan.n_row, plan.nt,
+                  _lib.ptr(scale), st)
+    D = torch.empty((B * plan.n_row, 2 * plan.n_fb), dtype=torch.float64, device=dev)
+    _lib.call("dvh_disp_tdft", _lib.ptr(rows), rows.stride(0), rows.stride(1), B, plan.n_row, plan.nt,
+              _lib.ptr(plan.tables(dev)["wt"]), plan.n_fb, _lib.ptr(scale), _lib.ptr(D), st)
+    return D
+
+
+def _slant_launch(D, plan: SlantPlan, B, out, v0=0, v1=None):
+    """dvh_disp_slant for the velocities [v0, v1) into ``out`` [B, v1 - v0, nF] (contiguous float32)."""
+    v1 = plan.nV if v1 is None else v1
+    tb = plan.tables(out.device)
+    n_row = 0 if D is None else plan.n_row
+    if D is None:
+        D = torch.empty(2, dtype=torch.float64, device=out.device)  # never read: the sum has no rows
+    _lib.call("dvh_disp_slant", _lib.ptr(D), B, n_row, max(plan.n_fb, 1), 0, n_row, _lib.ptr(tb["fb"]),
+              _lib.ptr(tb["freqs"]), plan.nF, _lib.ptr(tb["vels"][v0:v1]), v1 - v0, plan.dx, _lib.ptr(out),
+              (v1 - v0) * plan.nF, _lib.stream_of(out.device))
+    return out
+
+
+def slant_maps(data, plan: SlantPlan, norm=True, out=None):
+    """map_fv_FD_slant_stack for every gather of the batch: [B, nV, nF] float32, rows in the plan's velocity order
+    (into ``out``, a contiguous float32 device tensor of that shape, when given)."""
+    D = _slant_spectra(data, plan, norm)
+    B = data.shape[0]
+    if out is None:
+        out = torch.empty((B, plan.nV, plan.nF), dtype=torch.float32, device=data.device)
+    elif (tuple(out.shape) != (B, plan.nV, plan.nF) or out.dtype != torch.float32 or not out.is_contiguous()
+          or out.device != data.device):
+        raise ValueError(f"out must be a contiguous float32 [{B}, {plan.nV}, {plan.nF}] tensor on the data's device")
+    if out.numel() == 0:
+        return out
+    return _slant_launch(D, plan, B, out)
+
+
+SLANT_CHUNK_BYTES = 256 << 20  # per-pass images held at a time by slant_class_means
+
+
+def slant_class_means(data, plan: SlantPlan, slots, n_slot, norm=True):
+    """Mean phase-shift image per class slot, sum(images) / len over the slot's passes in batch order
+    ([n_slot, nV, nF] float32; a slot without passes is 0).  The magnitude is not linear in the data, so the per-pass
+    images are formed -- for a chunk of velocities at a time, SLANT_CHUNK_BYTES of images -- and averaged by
+    dvh_select_mean_var, each chunk into its rows of the result."""
+    slots = np.asarray(slots, dtype=np.int64)
+    B = data.shape[0]
+    if slots.shape != (B,) or (B and (slots.min() < 0 or slots.max() >= n_slot)):
+        raise ValueError("slant_class_means: one class slot in [0, n_slot) per gather")
+    dev = data.device
+    D = _slant_spectra(data, plan, norm)
+    nV, nF = plan.nV, plan.nF
+    out = torch.zeros((n_slot, nV, nF), dtype=torch.float32, device=dev)
+    if B == 0 or out.numel() == 0:
+        return out
+    counts = np.bincount(slots, minlength=n_slot)
+    filled = np.flatnonzero(counts)
+    cnt = counts[filled].astype(np.int32)
+    off = (np.cumsum(cnt) - cnt).astype(np.int32)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    sel_t, off_t, cnt_t = t(np.argsort(slots, kind="stable").astype(np.int32)), t(off), t(cnt)
+    means = out if filled.size == n_slot else torch.empty((filled.size, nV, nF), dtype=torch.float32, device=dev)
+    vc = int(max(1, min(nV, SLANT_CHUNK_BYTES // (4 * B * nF))))
+    img = torch.empty(B * vc * nF, dtype=torch.float32, device=dev)
+    for v0 in range(0, nV, vc):
+        v1 = min(nV, v0 + vc)
+        _slant_launch(D, plan, B, img[:B * (v1 - v0) * nF].view(B, v1 - v0, nF), v0, v1)
+        _lib.call("dvh_select_mean_var", _lib.ptr(img), (v1 - v0) * nF, (v1 - v0) * nF, _lib.ptr(sel_t), _lib.ptr(off_t),
+                  _lib.ptr(cnt_t), filled.size, _lib.ptr(means[:, v0:v1]), nV * nF, _lib.stream_of(dev))
+    if means is not out:
+        out[t(filled)] = means
+    return out

@@ -2,7 +2,9 @@
 
   fk            modules/utils.py:236-248  -> full |FK| grid from the dispersion GEMMs
   map_fv        modules/utils.py:457-475  -> dvh_disp_tdft / dvh_disp_fk / dvh_disp_fv
-  Dispersion    modules/utils.py:383-426  (same constructor, attributes, npz format, arithmetic)
+  map_fv_FD_slant_stack modules/utils.py:429-454 -> dvh_disp_row_l1 / dvh_disp_tdft / dvh_disp_slant
+  Dispersion    modules/utils.py:383-426  (same constructor, attributes, npz format, arithmetic; transform="slant"
+                stores the phase-shift image instead of map_fv's)
   bandpass_data modules/utils.py:179-189  -> dvh_sosfiltfilt (zero-phase order-10 Butterworth)
   extract_ridge_ref_idx modules/utils.py:621-678 -> dvh_ridge (one wave per ridge)
   win_avg_psd   modules/utils.py:715-728  -> dvh_welch_rows (one launch per window shape, das_diff_veh_amd.spectra)
@@ -99,14 +101,43 @@ def map_fv(data, dx, dt, freqs, vels, norm=False):
     return fv_maps(t, plan, norm=norm)[0].to("cpu").numpy()
 
 
+def slant_plan(nch, nt, dx, dt, freqs, vels, rows=(6, 25)):
+    from ..disp import SlantPlan
+    freqs = np.asarray(freqs, dtype=np.float64)
+    vels = np.asarray(vels, dtype=np.float64)
+    key = ("slant", nch, nt, float(dx), float(dt), freqs.tobytes(), vels.tobytes(), tuple(rows))
+    if key not in _PLANS:
+        if len(_PLANS) > 64:
+            _PLANS.clear()
+        _PLANS[key] = SlantPlan(nch, nt, dx, dt, freqs, vels, rows=rows)
+    return _PLANS[key]
+
+
+def map_fv_FD_slant_stack(data, dx, dt, freqs, vels, norm=True):
+    """Phase-shift (frequency-domain slant-stack) image [Nvel, Nfreq] of rows [6:25] of the gather, rows in the
+    caller's velocity order: float64 holding the float32 values the device stores (dvh_disp_slant).  A velocity of 0
+    raises ValueError, as in the reference."""
+    from ..disp import slant_maps
+    t = _as_device_batch(data)
+    plan = slant_plan(t.shape[1], t.shape[2], dx, dt, freqs, vels)
+    return slant_maps(t, plan, norm=norm)[0].to("cpu").numpy().astype(np.float64)
+
+
 class Dispersion:
-    def __init__(self, data, dx, dt, freqs, vels, norm=False, compute_fv=True):
+    """``transform`` selects the image: "fk" (default) is map_fv; "slant" is the phase-shift transform of
+    map_fv_FD_slant_stack over all rows of ``data``, stored with rows in descending velocity (map_fv's row
+    convention), so the ridge walk and save_to_npz consume it as they consume an f-k image."""
+
+    def __init__(self, data, dx, dt, freqs, vels, norm=False, compute_fv=True, transform="fk"):
+        if transform not in ("fk", "slant"):
+            raise ValueError(f"transform must be 'fk' or 'slant', not {transform!r}")
         self.data = data
         self.dx = dx
         self.dt = dt
         self.freqs = freqs
         self.vels = vels
         self.norm = norm
+        self.transform = transform
         if compute_fv:
             self._map_fv()
 
@@ -121,6 +152,13 @@ class Dispersion:
         return obj
 
     def _map_fv(self):
+        if self.transform == "slant":
+            from ..disp import slant_maps
+            t = _as_device_batch(self.data)
+            plan = slant_plan(t.shape[1], t.shape[2], self.dx, self.dt, self.freqs,
+                              np.sort(np.asarray(self.vels, dtype=np.float64))[::-1], rows=(0, t.shape[1]))
+            self.fv_map = slant_maps(t, plan, norm=self.norm)[0].to("cpu").numpy()
+            return
         self.fv_map = map_fv(self.data, self.dx, self.dt, freqs=self.freqs, vels=self.vels, norm=self.norm)
 
     def plot_image(self, *args, **kwargs):

@@ -180,6 +180,18 @@ int dvh_disp_fv_mfma(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, co
                      int32_t nF, int32_t nV, const double* fw, const double* sg, int32_t sgl, int32_t G, float* fv,
                      void* stream);
 
+/* Phase-shift (frequency-domain slant-stack) transform, map_fv_FD_slant_stack (modules/utils.py:429-454):
+ * fv[b][v][f] = float32(| sum_{r < n_row} D[b*nch + row0 + r][fb[f]] * exp(+i 2 pi freqs[f] (dx r) / vels[v]) |),
+ * D as dvh_disp_tdft writes it ([B*nch][2*n_fb] float64, re/im interleaved), fb[nF] the column of D for each frequency,
+ * images b_stride floats apart.  n_row == 0 writes zeros.  freqs, vels, fb are device arrays.
+ * Float64 throughout (sincos, the steering powers by recurrence, the sum in ascending row order), rounded once at the
+ * store; an image does not depend on the batch it is part of.  -2 for negative counts, row0 + n_row > nch, n_fb <= 0
+ * or overlapping images (B > 1 and b_stride < nF * nV); fv is then not written.  The caller validates fb against
+ * n_fb on the host. */
+int dvh_disp_slant(const double* D, int32_t B, int32_t nch, int32_t n_fb, int32_t row0, int32_t n_row,
+                   const int32_t* fb, const double* freqs, int32_t nF, const double* vels, int32_t nV, double dx,
+                   float* fv, int64_t b_stride, void* stream);
+
 /* ---------------------------------------------------------------- bootstrap / convergence
  * bootstrap_disp (apis/imaging_classes.py:8-48): per-pass gathers once, then per resample the mean
  * stack, its f-v image (dvh_disp_*) and the ridge picks (extract_ridge_ref_idx, modules/utils.py:621-678). */
