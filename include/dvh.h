@@ -409,6 +409,43 @@ int dvh_welch_rows(const float* x, int64_t n_groups, int64_t group_stride, int32
                    int32_t n_t, const double* win, int32_t nperseg, int32_t nfft, double scale, const double* tab,
                    double* out, void* ws, void* stream);
 
+/* ---------------------------------------------------------------- vehicle classes
+ * The notebooks' class split (imaging_diff_speed.ipynb cells 5-11, imaging_diff_weight.ipynb cells 5-11): the
+ * quasi-static curve and peak of every pass, and the per-class mean and std curves.  The thresholds on the peaks and
+ * speeds are host work (das_diff_veh_amd.classes). */
+
+/* Interior outputs per block of the Savitzky-Golay stage of dvh_qs_curves, and the longest window it takes. */
+#define DVH_QS_TILE 512
+#define DVH_QS_MAX_WLEN 255
+
+/* Per pass p < n_pass, all in float64:
+ *   m[t]   = (sum_c x[row_off[p][c] + t]) / n_ch      c = 0 .. n_ch - 1 in order, one division (np.mean(axis=0))
+ *   y      = savgol_filter(m, wlen, order) as the three maps h [wlen], el, er [wlen / 2][wlen] of dvh_savgol_rows
+ *   z      = scipy.signal.detrend(y): y minus its least-squares line on [(t + 1) / n_t, 1], in closed form
+ *   curve  = z - z[0],   peaks[p] = max_t |curve[t]|
+ * x: float32 (dtype 0) or float64 (1) samples; row_off [n_pass][n_ch] (device) holds the element offset from x of the
+ * first of the n_t samples of every row: (p n_ch + c) n_t for a contiguous batch, (ch0 + c) row_stride + t_start[p][c]
+ * for rows cut from a record.  Rows may overlap and start at any element alignment.  The table is the caller's to
+ * check: the kernel trusts it.  curves (nullable: peaks only): [n_pass] rows of curve_stride >= n_t doubles, nothing
+ * is written between them.  A pass whose curve holds a non-finite value gets peaks[p] = NaN and status[p] |= 1
+ * (status: nullable, n_pass int32 the caller has zeroed); other passes are not affected.  Every sum has a fixed order
+ * that depends on (n_ch, n_t, wlen) alone, and no atomics are used: a pass's curve and peak do not depend on n_pass, on
+ * its position, or on where its rows lie.  ws: dvh_qs_curves_workspace bytes.
+ * -4, nothing launched: wlen even, < 3 or > DVH_QS_MAX_WLEN, n_t < wlen, n_ch < 1, n_pass < 0.  n_pass = 0 returns 0
+ * without a launch. */
+int64_t dvh_qs_curves_workspace(int32_t n_pass, int32_t n_t);
+int dvh_qs_curves(const void* x, int32_t dtype, const int64_t* row_off, int32_t n_pass, int32_t n_ch, int32_t n_t,
+                  const double* h, int32_t wlen, const double* el, const double* er, double* curves,
+                  int64_t curve_stride, double* peaks, int32_t* status, void* ws, void* stream);
+
+/* np.mean(states, axis=0) and np.std(states, axis=0) (population, two passes) over the passes of every class slot:
+ * curves [n_pass] rows of curve_stride doubles, slots [n_pass] device int32 (a pass with a slot outside
+ * 0 .. n_slot - 1, -1 by convention, is in no class) -> mean, std [n_slot][n_t] and count [n_slot].  The sums run in
+ * pass order in float64, squares formed before they are added, as NumPy does; an empty slot gives NaN rows and
+ * count 0. */
+int dvh_class_curve_stats(const double* curves, int64_t curve_stride, const int32_t* slots, int32_t n_pass,
+                          int32_t n_t, int32_t n_slot, double* mean, double* std, int32_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
