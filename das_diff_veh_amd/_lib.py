@@ -38,6 +38,11 @@ SIGNATURES = {
     "dvh_disp_fv": [_p, _i32, _i32, _i32, _p, _f64, _f64, _p, _i32, _i32, _p, _p, _p, _i32, _p, _p],
     "dvh_disp_fv_cells": [_p, _i32, _i32, _i32, _p, _f64, _f64, _p, _i32, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32,
                           _p, _p, _p, _p, _p],
+    "dvh_disp_fk_as": [_p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p],
+    "dvh_disp_fv_as": [_p, _i32, _i32, _i32, _p, _f64, _f64, _p, _i32, _i32, _p, _p, _p, _i32, _p, _i32, _i32, _p],
+    "dvh_disp_fv_pick": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p],
+    "dvh_disp_fv_cells_as": [_p, _i32, _i32, _i32, _p, _f64, _f64, _p, _i32, _i32, _p, _p, _i32, _i32, _i32, _i32,
+                             _i32, _p, _p, _p, _p, _i32, _p],
     "dvh_disp_fv_mfma": [_p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _p, _i32, _i32, _p, _p],
     "dvh_disp_slant": [_p, _i32, _i32, _i32, _i32, _i32, _p, _p, _i32, _p, _i32, _f64, _p, _i64, _p],
     "dvh_select_mean": [_p, _i64, _i64, _p, _i32, _i32, _p, _i64, _p],

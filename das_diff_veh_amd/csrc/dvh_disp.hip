@@ -106,14 +106,14 @@ __global__ __launch_bounds__(64) void tdft_gemm_kernel(const float* __restrict__
 // the next chunk's while this one is multiplied; chunk row 8 q + s sits in LDS row 4 s + q, so the four
 // lane groups of one B-operand read hit rows next to each other (other bank halves), not 8 rows apart
 // (the same banks; measured the same, 96-101 us either way).  No split-K: the tile is stored, not
-// accumulated.  512 gathers of 25 x 500: 176 -> 96 us against the split-K kernel (DVH_TDFT_ROWS=0).
+// accumulated.  512 gathers of 25 x 500: 176 -> 96 us against the split-K kernel.
 constexpr int kTdNT = 7;   // 16-column tiles per block (112 columns)
 constexpr int kTdKC = 32;  // k per chunk
 constexpr int kTdRows = 64;
 // Small problems (a few class stacks: configs[1]'s six class images make a handful of blocks of the form above, each
 // a chain of 32 chunk round trips, 56 us) split K over G wave groups of one block instead: group g multiplies the chunks
 // kc = g (mod G), the groups' sums are added in group order through LDS (deterministic, no atomics); 2 tiles per
-// block keep the 16-wave block within 128 VGPRs (4 tiles spilled 14).  DVH_TDFT_ROWS=2: never split (A/B).
+// block keep the 16-wave block within 128 VGPRs (4 tiles spilled 14).
 constexpr int kTdNTs = 2, kTdGs = 4;
 
 __host__ __device__ constexpr size_t tdft_rows_lds(int NT, int G) {
@@ -1145,11 +1145,10 @@ DVH_API int dvh_disp_tdft(const float* data, int64_t b_stride, int64_t ch_stride
   if (!data || !wt || !D) return set_error(-2, "null pointer argument");
   const int M = B * nch, N = 2 * n_fb;
   if (M <= 0 || N <= 0) return 0;
-  static const int rows_env = getenv("DVH_TDFT_ROWS") ? atoi(getenv("DVH_TDFT_ROWS")) : 1;
-  if (rows_env && (reinterpret_cast<uintptr_t>(wt) & 15) == 0) {  // N = 2 n_fb is even: 16-byte twiddle pieces
+  if ((reinterpret_cast<uintptr_t>(wt) & 15) == 0) {  // N = 2 n_fb is even: 16-byte twiddle pieces
     const int64_t blocks = (int64_t)((M + kTdRows - 1) / kTdRows) * ((N + kTdNT * 16 - 1) / (kTdNT * 16));
     // fewer blocks than a quarter of the CUs: the K-split form (16 waves per block)
-    const bool split = blocks * 4 < cu_count() && rows_env != 2;
+    const bool split = blocks * 4 < cu_count();
     const void* fn = split ? (const void*)tdft_rows_kernel<kTdNTs, kTdGs> : (const void*)tdft_rows_kernel<kTdNT, 1>;
     const int NT = split ? kTdNTs : kTdNT, G = split ? kTdGs : 1;
     const size_t lds = tdft_rows_lds(NT, G);
@@ -1172,18 +1171,19 @@ DVH_API int dvh_disp_tdft(const float* data, int64_t b_stride, int64_t ch_stride
   return last_launch();
 }
 
-DVH_API int dvh_disp_fk(const double* D, int32_t B, int32_t nch, int32_t n_fb, const double* atab, int32_t MT,
-                        int32_t K2, int32_t n_kb, double* FK, const int32_t* slot, const float* weight,
-                        int32_t n_slot, void* stream) {
+DVH_API int dvh_disp_fk_as(const double* D, int32_t B, int32_t nch, int32_t n_fb, const double* atab, int32_t MT,
+                           int32_t K2, int32_t n_kb, double* FK, const int32_t* slot, const float* weight,
+                           int32_t n_slot, int32_t form, void* stream) {
   if (!D || !atab || !FK) return set_error(-2, "null pointer argument");
   if ((slot == nullptr) != (weight == nullptr)) return set_error(-2, "slot and weight go together");
   if (slot && n_slot <= 0) return set_error(-2, "slot accumulation needs n_slot > 0");
   if (MT % 16 || n_kb > MT || K2 < 2 * nch || K2 % 4) return set_error(-2, "invalid contraction table shape");
+  if (form < DVH_FK_FORM_AUTO || form > DVH_FK_FORM_TILED) return set_error(-2, "unknown contraction form");
   if (B <= 0 || n_fb <= 0) return 0;
   const size_t lds = sizeof(double) * ((size_t)K2 * (kFN + 1) + (size_t)2 * MT * (kFN + 1));
-  // the operand and the result no longer fit one block: tile m, chunk the channels (DVH_FK_TILED=1: always, A/B)
-  const char* tiled_env = getenv("DVH_FK_TILED");
-  if (lds > 160 * 1024 || (tiled_env && atoi(tiled_env) > 0)) {
+  if (form == DVH_FK_FORM_ONE_BLOCK && lds > 160 * 1024) return set_error(-4, "contraction table too large for one block");
+  // the operand and the result no longer fit one block: tile m, chunk the channels
+  if (lds > 160 * 1024 || form == DVH_FK_FORM_TILED) {
     const int64_t n_ft = (n_fb + kFN - 1) / kFN, n_mt = (n_kb + kFtM - 1) / kFtM;
     if (n_ft * n_mt > 0x7fffffff) return set_error(-4, "FK grid too large for one launch");
     hipLaunchKernelGGL(fk_contract_tiled_kernel, dim3((unsigned)(n_ft * n_mt), B), dim3(256), 0, (hipStream_t)stream, D,
@@ -1197,22 +1197,35 @@ DVH_API int dvh_disp_fk(const double* D, int32_t B, int32_t nch, int32_t n_fb, c
   return last_launch();
 }
 
-DVH_API int dvh_disp_fv(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const double* kgrid, double kmin,
-                        double kmax, const double* kq, int32_t nF, int32_t nV, const int32_t* fj, const double* fw,
-                        const double* sg, int32_t sgl, float* fv, void* stream) {
-  if (!FK || !kgrid || !kq || !fj || !fw || !sg || !fv) return set_error(-2, "null pointer argument");
-  if (n_kb < 2 || n_fb < 2) return set_error(-2, "FK grid needs at least 2 x 2 bins");
-  if (sgl % 2 == 0 || sgl > nF) return set_error(-4, "savgol window must be odd and <= number of frequencies");
-  if (B <= 0 || nV <= 0) return 0;
+DVH_API int dvh_disp_fk(const double* D, int32_t B, int32_t nch, int32_t n_fb, const double* atab, int32_t MT,
+                        int32_t K2, int32_t n_kb, double* FK, const int32_t* slot, const float* weight,
+                        int32_t n_slot, void* stream) {
+  return dvh_disp_fk_as(D, B, nch, n_fb, atab, MT, K2, n_kb, FK, slot, weight, n_slot, DVH_FK_FORM_AUTO, stream);
+}
+
+namespace {
+
+// What dvh_disp_fv_as launches for one shape: the kernel, its images per block and its launch figures.
+struct FvPick {
+  int form;    // DVH_FV_TILED, DVH_FV_BATCHED or DVH_FV_PER_IMAGE
+  int G;       // images per block (0: the per-image kernel)
+  int TO, nt;  // tiled: outputs per tile, tiles
+  int n_grp;   // batched: velocity groups per block
+  size_t lds;
+};
+
+// The choice among the three kernels of dvh_disp_fv, host arithmetic only.  `form` DVH_FV_AUTO takes each kernel
+// where it pays; a forced form drops the size thresholds (work, B * nvc) but never the structural conditions (LDS,
+// tile widths): where those fail the chain goes on, tiled -> batched -> per-image.  images_per_block > 0 sets G of
+// the forced kernel (DVH_FV_TILED, DVH_FV_BATCHED).
+FvPick fv_pick(int B, int n_kb, int n_fb, int nF, int nV, int sgl, int form, int images_per_block) {
   // batched kernel: weights computed once per (f, v) and reused over G images of the block
   // frequency-tiled kernel: tiles of TO outputs (multiple of 4, ~200), the last one >= kSgPad + 1
-  {
+  if (form == DVH_FV_AUTO || form == DVH_FV_TILED) {
     const int nt = (nF + 199) / 200;
     int TO = (nF + nt - 1) / nt;
     TO = (TO + 3) & ~3;
     const int last = nF - (nt - 1) * TO;
-    int mode = 1;  // the frequency-tiled kernel where it pays (below)
-    if (const char* ev = getenv("DVH_FV_TILE")) mode = atoi(ev);  // A/B: 0 = batched / per-image, 2 = always tiled
     const size_t lds_t = sizeof(double) * (size_t)(((size_t)n_kb * n_fb + 1) & ~(size_t)1) +
                          sizeof(double) * (size_t)((sgl * sgl + 1) & ~1) +
                          sizeof(float) * (size_t)kTileVT * (2 * kSgPad + kTileThreads + 4);
@@ -1221,30 +1234,23 @@ DVH_API int dvh_disp_fv(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb,
     // tiles under 160 outputs (nF = 242: 2 x 124) half the block idles -- the batched kernel packs
     // 4 velocity groups there (sliding bench 16.2 vs 17.6 ms per step)
     const int64_t work = (int64_t)B * nt * ((nV + kFvVT - 1) / kFvVT);  // in 4-velocity units
-    if (mode && ((work >= 8192 && TO >= 160) || mode > 1) && last >= kSgPad + 1 && TO + 2 * kSgPad <= kTileThreads &&
-        nF >= sgl && lds_t <= 64 * 1024) {
-      constexpr int VT = kTileVT;
-      if (int rc = set_dynamic_lds((const void*)fv_tile_kernel<VT, false>, lds_t)) return rc;
-      const int nvc = (nV + VT - 1) / VT;
+    if (((work >= 8192 && TO >= 160) || form == DVH_FV_TILED) && last >= kSgPad + 1 &&
+        TO + 2 * kSgPad <= kTileThreads && nF >= sgl && lds_t <= 64 * 1024) {
+      const int nvc = (nV + kTileVT - 1) / kTileVT;
       const int64_t pairs = (int64_t)nt * nvc;
       int G = (int)((pairs * B + 8191) / 8192);  // ~8 k blocks, at most 64 images each
       G = G < 1 ? 1 : (G > 64 ? 64 : G);
-      if (const char* ev = getenv("DVH_FV_TG")) G = atoi(ev) > 0 ? atoi(ev) : G;
-      dim3 grid(nt, nvc, (B + G - 1) / G);
-      hipLaunchKernelGGL((fv_tile_kernel<VT, false>), grid, dim3(kTileThreads), lds_t, (hipStream_t)stream, FK, B, G,
-                         n_kb, n_fb, kgrid, kmin, kmax, kq, nF, nV, TO, fj, fw, sg, sgl, fv, nullptr, nullptr, 0,
-                         nullptr);
-      return last_launch();
+      if (form == DVH_FV_TILED && images_per_block > 0) G = images_per_block;
+      return {DVH_FV_TILED, G, TO, nt, 0, lds_t};
     }
   }
   int n_grp = nF <= kFvThreads ? kFvThreads / nF : 0;
   n_grp = n_grp > 8 ? 8 : n_grp;
-  if (n_grp > 0) {
+  if (n_grp > 0 && form != DVH_FV_PER_IMAGE) {
     const int VC = kFvVT * n_grp;
     const size_t lds_b = 2 * sizeof(double) * (size_t)(((size_t)n_kb * n_fb + 1) & ~(size_t)1) +
                          sizeof(double) * (size_t)((sgl * sgl + 1) & ~1) + sizeof(float) * (size_t)VC * (((nF + 3) & ~3) + 2 * kSgPad);
     if ((int64_t)n_kb * n_fb <= (int64_t)kFvPre * kFvThreads && lds_b <= 150 * 1024) {
-      if (int rc = set_dynamic_lds((const void*)fv_batch_kernel, lds_b)) return rc;
       const int nvc = (nV + VC - 1) / VC;
       // images per block: enough blocks to fill the chip (>= ~2048), at most 16 images each
       // images per block: 1 024 blocks (4 per CU) amortise the per-block weights best (measured
@@ -1252,30 +1258,83 @@ DVH_API int dvh_disp_fv(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb,
       // per-image kernel's 256-thread blocks fill the chip better
       int G = (int)(((int64_t)B * nvc + 1023) / 1024);
       G = G < 1 ? 1 : (G > 64 ? 64 : G);
-      if ((int64_t)B * nvc < 1024) G = 0;
-      if (const char* ev = getenv("DVH_FV_G")) G = atoi(ev);  // A/B: images per block (0: per-image kernel)
-      if (G > 0) {
-      dim3 grid(nvc, (B + G - 1) / G);
-      hipLaunchKernelGGL(fv_batch_kernel, grid, dim3(kFvThreads), lds_b, (hipStream_t)stream, FK, B, G, n_kb, n_fb,
-                         kgrid, kmin, kmax, kq, nF, nV, n_grp, fj, fw, sg, sgl, fv);
-      return last_launch();
-      }
+      if ((int64_t)B * nvc < 1024 && form != DVH_FV_BATCHED) G = 0;
+      if (form == DVH_FV_BATCHED && images_per_block > 0) G = images_per_block;
+      if (G > 0) return {DVH_FV_BATCHED, G, 0, 0, n_grp, lds_b};
     }
   }
-  const size_t lds = sizeof(float) * (size_t)nF * kVS;
-  if (lds > 160 * 1024) return set_error(-4, "too many frequencies for one block");
-  if (int rc = set_dynamic_lds((const void*)fv_kernel, lds)) return rc;
+  return {DVH_FV_PER_IMAGE, 0, 0, 0, 0, sizeof(float) * (size_t)nF * kVS};
+}
+
+int fv_check(int32_t n_kb, int32_t n_fb, int32_t nF, int32_t sgl, int32_t form) {
+  if (n_kb < 2 || n_fb < 2) return set_error(-2, "FK grid needs at least 2 x 2 bins");
+  if (sgl < 1 || sgl % 2 == 0 || sgl > nF)
+    return set_error(-4, "savgol window must be odd and <= number of frequencies");
+  if (form < DVH_FV_AUTO || form > DVH_FV_TILED) return set_error(-2, "unknown f-v form");
+  return 0;
+}
+
+}  // namespace
+
+DVH_API int dvh_disp_fv_pick(int32_t B, int32_t n_kb, int32_t n_fb, int32_t nF, int32_t nV, int32_t sgl, int32_t form,
+                             int32_t images_per_block, int32_t* form_out, int32_t* G_out) {
+  if (!form_out || !G_out) return set_error(-2, "null pointer argument");
+  if (int rc = fv_check(n_kb, n_fb, nF, sgl, form)) return rc;
+  *form_out = DVH_FV_AUTO;  // no images or no velocities: nothing would run
+  *G_out = 0;
+  if (B <= 0 || nV <= 0) return 0;
+  const FvPick p = fv_pick(B, n_kb, n_fb, nF, nV, sgl, form, images_per_block);
+  if (p.form == DVH_FV_PER_IMAGE && p.lds > 160 * 1024) return set_error(-4, "too many frequencies for one block");
+  *form_out = p.form;
+  *G_out = p.G;
+  return 0;
+}
+
+DVH_API int dvh_disp_fv_as(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const double* kgrid, double kmin,
+                           double kmax, const double* kq, int32_t nF, int32_t nV, const int32_t* fj, const double* fw,
+                           const double* sg, int32_t sgl, float* fv, int32_t form, int32_t images_per_block,
+                           void* stream) {
+  if (!FK || !kgrid || !kq || !fj || !fw || !sg || !fv) return set_error(-2, "null pointer argument");
+  if (int rc = fv_check(n_kb, n_fb, nF, sgl, form)) return rc;
+  if (B <= 0 || nV <= 0) return 0;
+  const FvPick p = fv_pick(B, n_kb, n_fb, nF, nV, sgl, form, images_per_block);
+  const int G = p.G;
+  if (p.form == DVH_FV_TILED) {
+    constexpr int VT = kTileVT;
+    if (int rc = set_dynamic_lds((const void*)fv_tile_kernel<VT, false>, p.lds)) return rc;
+    dim3 grid(p.nt, (nV + VT - 1) / VT, (B + G - 1) / G);
+    hipLaunchKernelGGL((fv_tile_kernel<VT, false>), grid, dim3(kTileThreads), p.lds, (hipStream_t)stream, FK, B, G,
+                       n_kb, n_fb, kgrid, kmin, kmax, kq, nF, nV, p.TO, fj, fw, sg, sgl, fv, nullptr, nullptr, 0,
+                       nullptr);
+    return last_launch();
+  }
+  if (p.form == DVH_FV_BATCHED) {
+    if (int rc = set_dynamic_lds((const void*)fv_batch_kernel, p.lds)) return rc;
+    const int VC = kFvVT * p.n_grp;
+    dim3 grid((nV + VC - 1) / VC, (B + G - 1) / G);
+    hipLaunchKernelGGL(fv_batch_kernel, grid, dim3(kFvThreads), p.lds, (hipStream_t)stream, FK, B, G, n_kb, n_fb,
+                       kgrid, kmin, kmax, kq, nF, nV, p.n_grp, fj, fw, sg, sgl, fv);
+    return last_launch();
+  }
+  if (p.lds > 160 * 1024) return set_error(-4, "too many frequencies for one block");
+  if (int rc = set_dynamic_lds((const void*)fv_kernel, p.lds)) return rc;
   dim3 grid((nV + kVC - 1) / kVC, B);
-  hipLaunchKernelGGL(fv_kernel, grid, dim3(256), lds, (hipStream_t)stream, FK, n_kb, n_fb, kgrid, kmin, kmax, kq, nF,
+  hipLaunchKernelGGL(fv_kernel, grid, dim3(256), p.lds, (hipStream_t)stream, FK, n_kb, n_fb, kgrid, kmin, kmax, kq, nF,
                      nV, fj, fw, sg, sgl, fv);
   return last_launch();
 }
 
-DVH_API int dvh_disp_fv_cells(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const double* kgrid, double kmin,
-                              double kmax, const double* kq, int32_t nF, int32_t nV, const double* fw, const double* sg,
-                              int32_t sgl, int32_t TO, int32_t n_tile, int32_t VT, int32_t max_cell,
-                              const int32_t* cell_off, const int32_t* n_cell, const int32_t* qidx, float* fv,
-                              void* stream) {
+DVH_API int dvh_disp_fv(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const double* kgrid, double kmin,
+                        double kmax, const double* kq, int32_t nF, int32_t nV, const int32_t* fj, const double* fw,
+                        const double* sg, int32_t sgl, float* fv, void* stream) {
+  return dvh_disp_fv_as(FK, B, n_kb, n_fb, kgrid, kmin, kmax, kq, nF, nV, fj, fw, sg, sgl, fv, DVH_FV_AUTO, 0, stream);
+}
+
+DVH_API int dvh_disp_fv_cells_as(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const double* kgrid,
+                                 double kmin, double kmax, const double* kq, int32_t nF, int32_t nV, const double* fw,
+                                 const double* sg, int32_t sgl, int32_t TO, int32_t n_tile, int32_t VT,
+                                 int32_t max_cell, const int32_t* cell_off, const int32_t* n_cell, const int32_t* qidx,
+                                 float* fv, int32_t images_per_block, void* stream) {
   if (!FK || !kgrid || !kq || !fw || !sg || !fv || !cell_off || !n_cell || !qidx)
     return set_error(-2, "null pointer argument");
   if (n_kb < 2 || n_fb < 2) return set_error(-2, "FK grid needs at least 2 x 2 bins");
@@ -1299,12 +1358,21 @@ DVH_API int dvh_disp_fv_cells(const double* FK, int32_t B, int32_t n_kb, int32_t
   const int64_t pairs = (int64_t)n_tile * nvc;
   int G = (int)((pairs * B + 8191) / 8192);  // ~8 k blocks, at most 64 images each
   G = G < 1 ? 1 : (G > 64 ? 64 : G);
-  if (const char* ev = getenv("DVH_FV_TG")) G = atoi(ev) > 0 ? atoi(ev) : G;
+  if (images_per_block > 0) G = images_per_block;
   dim3 grid(n_tile, nvc, (B + G - 1) / G);
   hipLaunchKernelGGL((fv_tile_kernel<kFvVT, true>), grid, dim3(kTileThreads), lds, (hipStream_t)stream, FK, B, G, n_kb,
                      n_fb, kgrid, kmin, kmax, kq, nF, nV, TO, (const int32_t*)nullptr, fw, sg, sgl, fv, cell_off, n_cell,
                      max_cell, (const int4*)qidx);
   return last_launch();
+}
+
+DVH_API int dvh_disp_fv_cells(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const double* kgrid, double kmin,
+                              double kmax, const double* kq, int32_t nF, int32_t nV, const double* fw, const double* sg,
+                              int32_t sgl, int32_t TO, int32_t n_tile, int32_t VT, int32_t max_cell,
+                              const int32_t* cell_off, const int32_t* n_cell, const int32_t* qidx, float* fv,
+                              void* stream) {
+  return dvh_disp_fv_cells_as(FK, B, n_kb, n_fb, kgrid, kmin, kmax, kq, nF, nV, fw, sg, sgl, TO, n_tile, VT, max_cell,
+                              cell_off, n_cell, qidx, fv, 0, stream);
 }
 
 DVH_API int dvh_disp_fv_mfma(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const double* hx,

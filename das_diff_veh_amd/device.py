@@ -19,7 +19,7 @@ def default_device():
 # by a thread pool into one of two pinned buffers (in the windows' own dtype, no host-side conversion), sent
 # by an asynchronous H2D copy on a side stream, and converted to float32 on the device, so that the host copy
 # of chunk k + 1 runs while chunk k crosses PCIe.
-STAGE_BYTES = int(os.environ.get("DVH_STAGE_MB", "64")) << 20  # 64 MB: 36.2-36.3 k vs 35.0-35.4 k windows/s at 128
+STAGE_BYTES = 64 << 20  # 64 MB: 36.2-36.3 k vs 35.0-35.4 k windows/s at 128
 _STAGE = {}
 # One staging at a time per (device, dtype): the pinned and device chunk buffers are shared by every caller (the
 # background thread of stage_async and the caller's own to_device_f32), so a staging holds its stager's lock from
@@ -67,10 +67,8 @@ atexit.register(lambda: sync_staging() if torch.cuda.is_initialized() else None)
 import ctypes  # noqa: E402
 
 _NTHREADS = max(1, min(16, os.cpu_count() or 1))
-# the host copy into pinned memory: native (dvh_host_gather on the thread pool, float32 C-contiguous windows;
-# others take the pool path) | pool (np.copyto per window on the thread pool) | torch (torch.stack)
-STAGE_MODE = os.environ.get("DVH_STAGE_MODE", "native")
-STAGE_RAMP = int(os.environ.get("DVH_STAGE_RAMP", "0"))  # 0: off, r: first chunk k / r windows, doubling up to k
+# the host copy into pinned memory runs on the thread pool: dvh_host_gather for C-contiguous windows of the batch's
+# dtype, np.copyto per window for the others
 
 
 def _pool():
@@ -105,38 +103,29 @@ def stage_windows(hosts, device, out=None, wait=True):
 def _stage_chunks(hosts, st, out, n, shape, src, per, k, device, wait):
     pool = _pool()
     tdt = torch.float32 if src == np.float32 else torch.float64
-    # chunk starts: with STAGE_RAMP = r the first chunks are k / r, 2 k / r, ... windows, so that the first H2D
-    # copy starts after a short host copy instead of a full one
-    starts, a, kc = [], 0, max(1, k // STAGE_RAMP) if STAGE_RAMP > 0 else k
-    while a < n:
-        starts.append((a, min(kc, n - a)))
-        a += kc
-        kc = min(k, 2 * kc)
-    for ci, (a, kk) in enumerate(starts):
+    for ci, a in enumerate(range(0, n, k)):
+        kk = min(k, n - a)
         b = ci & 1
         st["free"][b].synchronize()  # the H2D that last read this pinned buffer is done
-        if STAGE_MODE == "torch":  # torch's parallel CPU cat into the pinned buffer
-            pin_t = st["pinned"][b][:kk * per].view(tdt).view((kk,) + tuple(shape))
-            torch.stack([torch.from_numpy(np.ascontiguousarray(h, dtype=src)) for h in hosts[a:a + kk]], out=pin_t)
-        else:  # thread pool, contiguous runs of windows per task
-            view = st["pinned"][b].numpy()[:kk * per].view(src).reshape((kk,) + tuple(shape))
-            nt = min(kk, _NTHREADS)
-            bounds = [kk * q // nt for q in range(nt + 1)]
-            chunk = hosts[a:a + kk]
-            if STAGE_MODE == "native" and all(h.dtype == src and h.flags.c_contiguous for h in chunk):
-                from . import _lib
-                srcs = (ctypes.c_void_p * kk)(*[h.ctypes.data for h in chunk])
-                base = view.ctypes.data
+        # thread pool, contiguous runs of windows per task
+        view = st["pinned"][b].numpy()[:kk * per].view(src).reshape((kk,) + tuple(shape))
+        nt = min(kk, _NTHREADS)
+        bounds = [kk * q // nt for q in range(nt + 1)]
+        chunk = hosts[a:a + kk]
+        if all(h.dtype == src and h.flags.c_contiguous for h in chunk):
+            from . import _lib
+            srcs = (ctypes.c_void_p * kk)(*[h.ctypes.data for h in chunk])
+            base = view.ctypes.data
 
-                def run(q):  # one native call per thread: no interpreter work per window, the lock released
-                    j0, j1 = bounds[q], bounds[q + 1]
-                    _lib.call("dvh_host_gather", ctypes.c_void_p(base + j0 * per),
-                              ctypes.byref(srcs, j0 * ctypes.sizeof(ctypes.c_void_p)), per, j1 - j0)
-            else:
-                def run(q):
-                    for j in range(bounds[q], bounds[q + 1]):
-                        np.copyto(view[j], chunk[j], casting="unsafe")
-            list(pool.map(run, range(nt)))
+            def run(q):  # one native call per thread: no interpreter work per window, the lock released
+                j0, j1 = bounds[q], bounds[q + 1]
+                _lib.call("dvh_host_gather", ctypes.c_void_p(base + j0 * per),
+                          ctypes.byref(srcs, j0 * ctypes.sizeof(ctypes.c_void_p)), per, j1 - j0)
+        else:
+            def run(q):
+                for j in range(bounds[q], bounds[q + 1]):
+                    np.copyto(view[j], chunk[j], casting="unsafe")
+        list(pool.map(run, range(nt)))
         with torch.cuda.stream(st["stream"]):
             pin = st["pinned"][b][:kk * per].view(tdt).view((kk,) + tuple(shape))
             if src == np.float32:

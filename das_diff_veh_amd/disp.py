@@ -11,8 +11,8 @@ Every FLOP on the data runs in the kernels (das_diff_veh_amd/csrc/dvh_disp.hip).
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
-import os
 
 import numpy as np
 import scipy.signal
@@ -120,6 +120,11 @@ class DispPlan:
     # 12-sample halo (one tile when the whole axis fits the block)
     TILE_THREADS, TILE_VT, TILE_PAD = 256, 4, 12
 
+    def cell_tiles(self):
+        """(n_tile, TO) of the cell-staged blocks: tiles, and outputs per tile (a multiple of 4)."""
+        nt = 1 if self.nF <= self.TILE_THREADS else -(-self.nF // 200)
+        return nt, (-(-self.nF // nt) + 3) & ~3
+
     def cell_tables(self):
         """Per (velocity chunk, frequency tile) block of dvh_disp_fv_cells: the FK cells its bilinear stencils
         read -- rows m, m + 1 of columns j, j + 1 for every (f, v) it samples -- column-major (each column's
@@ -129,8 +134,7 @@ class DispPlan:
             return self._cells or None
         T, VT, pad = self.TILE_THREADS, self.TILE_VT, self.TILE_PAD
         nF, nV = self.nF, self.nV
-        nt = 1 if nF <= T else -(-nF // 200)
-        TO = (-(-nF // nt) + 3) & ~3
+        nt, TO = self.cell_tiles()
         ok = nF >= self.sgl
         nvc = -(-nV // VT)
         n_ct = nvc * nt
@@ -210,8 +214,12 @@ def _check(data, plan):
         raise ValueError(f"data must be [B, {plan.nch}, {plan.nt}] with a contiguous time axis")
 
 
-def fk_grid(data, plan: DispPlan, norm=False, slots=None, weights=None, n_slot=None):
-    """|FK| on the plan's compact grid: [B, n_kb, n_fb], or per-slot weighted sums [n_slot, ...]."""
+FK_FORMS = {None: 0, "one_block": 1, "tiled": 2}  # include/dvh.h DVH_FK_FORM_*
+
+
+def fk_grid(data, plan: DispPlan, norm=False, slots=None, weights=None, n_slot=None, contraction=None):
+    """|FK| on the plan's compact grid: [B, n_kb, n_fb], or per-slot weighted sums [n_slot, ...].  ``contraction``
+    names the channel-contraction kernel ("one_block", "tiled"; None: by table size, dvh_disp_fk's rule)."""
     _check(data, plan)
     dev = data.device
     tb = plan.tables(dev)
@@ -235,87 +243,110 @@ def fk_grid(data, plan: DispPlan, norm=False, slots=None, weights=None, n_slot=N
         FK = torch.zeros((n_slot, plan.n_kb, plan.n_fb), dtype=torch.float64, device=dev)
         sl = torch.as_tensor(slots.astype(np.int32), device=dev)
         wt = torch.as_tensor(np.asarray(weights, dtype=np.float32), device=dev)
-    _lib.call("dvh_disp_fk", _lib.ptr(D), B, plan.nch, plan.n_fb, _lib.ptr(tb["atab"]), plan.MT, plan.K2,
-              plan.n_kb, _lib.ptr(FK), _lib.ptr(sl), _lib.ptr(wt), 0 if n_slot is None else int(n_slot), st)
+    _lib.call("dvh_disp_fk_as", _lib.ptr(D), B, plan.nch, plan.n_fb, _lib.ptr(tb["atab"]), plan.MT, plan.K2,
+              plan.n_kb, _lib.ptr(FK), _lib.ptr(sl), _lib.ptr(wt), 0 if n_slot is None else int(n_slot),
+              FK_FORMS[contraction], st)
     return FK
 
 
-def _use_cells(plan: DispPlan, B: int) -> bool:
-    """The cell-staged tiled kernel for batches that fill the chip (>= 4 096 blocks); few images (the
-    bench's class stacks) keep the per-image kernel.  DVH_FV_CELLS=0 / 1 forces it off / on (A/B)."""
-    env = os.environ.get("DVH_FV_CELLS")
-    if env is not None:
-        return env != "0" and plan.cell_tables() is not None
-    if "DVH_FV_TILE" in os.environ or "DVH_FV_G" in os.environ:  # A/B of the dvh_disp_fv kernels
-        return False
-    nt = 1 if plan.nF <= DispPlan.TILE_THREADS else -(-plan.nF // 200)
-    if B * nt * -(-plan.nV // DispPlan.TILE_VT) < 4096:
-        return False
-    return plan.cell_tables() is not None
+MFMA_MIN_BLOCKS = 512  # (64-velocity block, image) pairs: two blocks per CU
+CELLS_MIN_BLOCKS = 4096  # (frequency tile, 4-velocity chunk, image) blocks: a batch that fills the chip
+
+# the kernels of the dvh_disp_fv chain by their include/dvh.h form (DVH_FV_*); "not_tiled" leaves the tiled kernel out
+_CHAIN = {"per_image": 1, "not_tiled": 2, "batched": 3, "tiled": 4}
+_CHAIN_NAME = {1: "per_image", 3: "batched", 4: "tiled"}
+FORMS = (None, "mfma", "cells", "chain", *_CHAIN)
+
+
+def _fv_staged(plan: DispPlan, B: int, form):
+    """"mfma" or "cells" where one of the two table-fed kernels runs, None for the dvh_disp_fv chain."""
+    if form not in FORMS:
+        raise ValueError(f"form must be one of {FORMS}")
+    # dvh_disp_fv_mfma: savgol window 25, nF >= 32, a compact FK grid of at most 8 192 bins
+    mfma_ok = plan.sgl == 25 and plan.nF >= 32 and plan.n_kb * plan.n_fb <= 8192
+    if mfma_ok and (form == "mfma" or (form is None and B * -(-plan.nV // 64) >= MFMA_MIN_BLOCKS)):
+        return "mfma"
+    # dvh_disp_fv_cells for batches that fill the chip; few images (the bench's class stacks) keep the chain
+    n_blocks = B * plan.cell_tiles()[0] * -(-plan.nV // DispPlan.TILE_VT)
+    if form == "cells" or (form in (None, "mfma") and n_blocks >= CELLS_MIN_BLOCKS):
+        if plan.cell_tables() is not None:
+            return "cells"
+    return None
+
+
+def fv_choice(plan: DispPlan, B: int, form=None, images_per_block=0):
+    """(name, G): the f-v kernel fv_from_fk launches for B images of the plan -- "mfma", "cells", "tiled", "batched" or
+    "per_image" -- and its images per block.  Host arithmetic only, no device.
+    form None is the product's choice: mfma from MFMA_MIN_BLOCKS blocks on, cells from CELLS_MIN_BLOCKS on, else the
+    dvh_disp_fv chain (tiled, batched, per-image by size: dvh_disp_fv_pick).  A form named by the caller (FORMS;
+    "chain" = dvh_disp_fv's own choice, "not_tiled" = batched or per-image by size) runs wherever the kernel's
+    structural conditions hold, whatever the batch size; where they do not, a refused "mfma" takes the product's
+    choice among the others and every other refused form the chain, down to per_image.  images_per_block > 0 sets G
+    of the kernel named by ``form``; G is 0 where the launcher counts for itself (mfma, cells) and for per_image."""
+    name = _fv_staged(plan, B, form)
+    if name is not None:
+        return name, int(images_per_block) if form == name else 0
+    f, g = C.c_int32(), C.c_int32()
+    _lib.call("dvh_disp_fv_pick", B, plan.n_kb, plan.n_fb, plan.nF, plan.nV, plan.sgl, _CHAIN.get(form, 0),
+              int(images_per_block), C.byref(f), C.byref(g))
+    return _CHAIN_NAME.get(f.value), g.value
 
 
 def _use_mfma(plan: DispPlan, B: int) -> bool:
-    """The MFMA-filter kernel (dvh_disp_fv_mfma) where it applies: savgol window 25, nF >= 32, a compact FK
-    grid of at most 8 192 bins.  DVH_FV_MFMA=0 / 1 forces it off / on (A/B)."""
-    ok = plan.sgl == 25 and plan.nF >= 32 and plan.n_kb * plan.n_fb <= 8192
-    env = os.environ.get("DVH_FV_MFMA")
-    if env is not None:
-        return env != "0" and ok
-    if any(k in os.environ for k in ("DVH_FV_TILE", "DVH_FV_G", "DVH_FV_CELLS")):  # A/B of the other kernels
-        return False
-    return ok and B * -(-plan.nV // 64) >= MFMA_MIN_BLOCKS
+    """fv_choice(plan, B)[0] == "mfma", under the name bench.py imports."""
+    return _fv_staged(plan, B, None) == "mfma"
 
 
-MFMA_MIN_BLOCKS = 512  # (64-velocity block, image) pairs: two blocks per CU
-
-
-def fv_from_fk(FK, plan: DispPlan, out=None):
+def fv_from_fk(FK, plan: DispPlan, out=None, form=None, images_per_block=0):
+    """The f-v images of |FK| [B, n_kb, n_fb] on the kernel fv_choice(plan, B, form, images_per_block) names."""
     dev = FK.device
     tb = plan.tables(dev)
     B = FK.shape[0]
     if out is None:
         out = torch.empty((B, plan.nV, plan.nF), dtype=torch.float32, device=dev)
-    if _use_mfma(plan, B):
+    name = _fv_staged(plan, B, form)
+    G = int(images_per_block) if form == name else 0
+    if name == "mfma":
         key = ("mfma", str(dev))
         if key not in plan._dev:
             mt = plan.mfma_tables()
             plan._dev[key] = {k: torch.from_numpy(v).to(dev) for k, v in mt.items()}
         mt = plan._dev[key]
-        G = int(os.environ.get("DVH_FV_MG", "0"))
         _lib.call("dvh_disp_fv_mfma", _lib.ptr(FK), B, plan.n_kb, plan.n_fb, _lib.ptr(mt["hx"]), _lib.ptr(mt["cb"]),
                   plan.nF, plan.nV, _lib.ptr(tb["fw"]), _lib.ptr(tb["sg"]), plan.sgl, G, _lib.ptr(out),
                   _lib.stream_of(dev))
         return out
-    if _use_cells(plan, B):
+    if name == "cells":
         key = ("cells", str(dev))
         if key not in plan._dev:
             ct = plan.cell_tables()
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
             plan._dev[key] = dict(ct, cell_off=t(ct["cell_off"]), n_cell=t(ct["n_cell"]), qidx=t(ct["qidx"]))
         c = plan._dev[key]
-        _lib.call("dvh_disp_fv_cells", _lib.ptr(FK), B, plan.n_kb, plan.n_fb, _lib.ptr(tb["kgrid"]), plan.kmin,
+        _lib.call("dvh_disp_fv_cells_as", _lib.ptr(FK), B, plan.n_kb, plan.n_fb, _lib.ptr(tb["kgrid"]), plan.kmin,
                   plan.kmax, _lib.ptr(tb["kq"]), plan.nF, plan.nV, _lib.ptr(tb["fw"]), _lib.ptr(tb["sg"]), plan.sgl,
                   c["TO"], c["n_tile"], DispPlan.TILE_VT, c["max_cell"], _lib.ptr(c["cell_off"]), _lib.ptr(c["n_cell"]),
-                  _lib.ptr(c["qidx"]), _lib.ptr(out), _lib.stream_of(dev))
+                  _lib.ptr(c["qidx"]), _lib.ptr(out), G, _lib.stream_of(dev))
         return out
-    _lib.call("dvh_disp_fv", _lib.ptr(FK), B, plan.n_kb, plan.n_fb, _lib.ptr(tb["kgrid"]), plan.kmin, plan.kmax,
+    _lib.call("dvh_disp_fv_as", _lib.ptr(FK), B, plan.n_kb, plan.n_fb, _lib.ptr(tb["kgrid"]), plan.kmin, plan.kmax,
               _lib.ptr(tb["kq"]), plan.nF, plan.nV, _lib.ptr(tb["fj"]), _lib.ptr(tb["fw"]), _lib.ptr(tb["sg"]),
-              plan.sgl, _lib.ptr(out), _lib.stream_of(dev))
+              plan.sgl, _lib.ptr(out), _CHAIN.get(form, 0), int(images_per_block), _lib.stream_of(dev))
     return out
 
 
-def fv_maps(data, plan: DispPlan, norm=False):
+def fv_maps(data, plan: DispPlan, norm=False, form=None, images_per_block=0):
     """map_fv for every gather of the batch: [B, Nvel, Nfreq] float32 (rows = sorted-query order)."""
-    return fv_from_fk(fk_grid(data, plan, norm=norm), plan)
+    return fv_from_fk(fk_grid(data, plan, norm=norm), plan, form=form, images_per_block=images_per_block)
 
 
-def fv_class_means(data, plan: DispPlan, slots, n_slot, norm=False, counts=None):
+def fv_class_means(data, plan: DispPlan, slots, n_slot, norm=False, counts=None, form=None, images_per_block=0):
     """Mean f-v image per class slot (sum(disps) / len): the transform after |FK| is linear, so the
     per-pass |FK| grids are averaged on device and sampled once per slot."""
     slots = np.asarray(slots, dtype=np.int64)
     counts = np.bincount(slots, minlength=n_slot) if counts is None else np.asarray(counts)
     w = np.where(counts[slots] > 0, 1.0 / np.maximum(counts[slots], 1), 0.0)
-    return fv_from_fk(fk_grid(data, plan, norm=norm, slots=slots, weights=w, n_slot=n_slot), plan)
+    return fv_from_fk(fk_grid(data, plan, norm=norm, slots=slots, weights=w, n_slot=n_slot), plan, form=form,
+                      images_per_block=images_per_block)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -10,8 +10,6 @@ stream-ordered on the current torch stream and never synchronise.
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
@@ -19,14 +17,13 @@ from . import _lib
 from .plan import VsgPlan
 
 # Stack launches at w = 500 take a workspace for the per-pass table of pivot-slice spectra, so that the rows
-# whose pivot slices it holds transform only their receivers (EngF500::spectra_tab); DVH_PIVOT_TABLE=0 runs
-# them without it (every sub-window z = pivot + i receiver; A/B timing).
-_TABLE = os.environ.get("DVH_PIVOT_TABLE", "1") != "0"
+# whose pivot slices it holds transform only their receivers (EngF500::spectra_tab); table=False runs them without
+# it (every sub-window z = pivot + i receiver).
 
 
-def spectra_workspace(plan: VsgPlan, device, cache: dict | None = None, table: bool | None = None):
+def spectra_workspace(plan: VsgPlan, device, cache: dict | None = None, table: bool = True):
     """The pivot-spectra workspace of a stack launch (None when the plan's w does not use one)."""
-    if not (_TABLE if table is None else table):
+    if not table:
         return None
     nbytes = int(_lib.load().dvh_vsg_stack_workspace(plan.n_pass, plan.w))
     if nbytes <= 0:
@@ -140,10 +137,10 @@ class StackSchedule:
 
 def vsg_stack(windows: torch.Tensor, plan: VsgPlan, schedule: StackSchedule, scales: torch.Tensor | None = None,
               out: torch.Tensor | None = None, accumulate: bool = False,
-              win_sumsq: torch.Tensor | None = None, table: bool | None = None) -> torch.Tensor:
+              win_sumsq: torch.Tensor | None = None, table: bool = True) -> torch.Tensor:
     """Class-mean gathers [n_slot, R, w]; with accumulate=True adds into ``out``.  ``scales`` come
     from vsg_scales (formed here with ``win_sumsq`` when not given).  ``table``: use the pivot-slice
-    spectra table (default: on unless DVH_PIVOT_TABLE=0)."""
+    spectra table (default: on)."""
     _check_windows(windows, plan)
     pass_tab, seg_tab = plan.device_tables(windows.device)
     order, chunk_tab, weights = schedule.device_tables(windows.device)

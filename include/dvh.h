@@ -144,11 +144,18 @@ int dvh_disp_tdft(const float* data, int64_t b_stride, int64_t ch_stride, int32_
  * slots (a slot outside [0, n_slot) is never written; callers validate slots on the host).
  * Any nch and n_kb: tables of up to 160 KB of LDS (8 * 33 * (K2 + 2 * MT) bytes, e.g. 128 channels x 127
  * wavenumbers) run one block per (gather, 32 f-bins); larger ones are tiled over 64 wavenumbers per block with
- * the channels chunked through LDS (DVH_FK_TILED=1: always, A/B), with the same sums in the same order.  What
+ * the channels chunked through LDS, with the same sums in the same order.  What
  * remains is the caller's dense atab (2 * MT * K2 doubles) and B <= 65535 gathers per launch.  -2 for a table
  * shape that breaks the rules above (MT % 16, n_kb > MT, K2 < 2 * nch, K2 % 4); FK is then not written. */
 int dvh_disp_fk(const double* D, int32_t B, int32_t nch, int32_t n_fb, const double* atab, int32_t MT, int32_t K2,
                 int32_t n_kb, double* FK, const int32_t* slot, const float* weight, int32_t n_slot, void* stream);
+
+/* dvh_disp_fk with the kernel named: AUTO is dvh_disp_fk's rule, TILED the tiled kernel at any table size (bitwise
+ * the one-block kernel's result), ONE_BLOCK the one-block kernel or -4 when the table needs more than 160 KB. */
+enum { DVH_FK_FORM_AUTO = 0, DVH_FK_FORM_ONE_BLOCK = 1, DVH_FK_FORM_TILED = 2 };
+int dvh_disp_fk_as(const double* D, int32_t B, int32_t nch, int32_t n_fb, const double* atab, int32_t MT, int32_t K2,
+                   int32_t n_kb, double* FK, const int32_t* slot, const float* weight, int32_t n_slot, int32_t form,
+                   void* stream);
 
 /* f-v sampling: fv[B][nV][nF] = savgol(float32(bilinear(FK; k = kq[f][v], f)))  with the
  * interp2d query order (kq sorted per frequency), FITPACK clamping to [kmin, kmax], the compact
@@ -157,6 +164,26 @@ int dvh_disp_fk(const double* D, int32_t B, int32_t nch, int32_t n_fb, const dou
 int dvh_disp_fv(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const double* kgrid, double kmin,
                 double kmax, const double* kq, int32_t nF, int32_t nV, const int32_t* fj, const double* fw,
                 const double* sg, int32_t sgl, float* fv, void* stream);
+
+/* The three kernels behind dvh_disp_fv, all with the same outputs: per-image (one block per image and 4 velocities),
+ * batched (G images per block share the per-(f, v) weights; nF <= 1024 and an FK grid of <= 4 096 bins) and
+ * frequency-tiled (tiles of ~200 outputs, G images per block; the FK grid and the filter within 64 KB of LDS).
+ * dvh_disp_fv is dvh_disp_fv_as(..., DVH_FV_AUTO, 0): each kernel where it measured fastest.  A named form drops
+ * the size thresholds of that choice, never a kernel's own limits: where the named kernel cannot run the chain
+ * goes on as under AUTO, tiled -> batched -> per-image.  DVH_FV_NOT_TILED leaves the tiled kernel out and chooses
+ * between the other two by size.  images_per_block > 0 sets G of the named kernel (TILED, BATCHED); 0 is the
+ * launcher's count. */
+enum { DVH_FV_AUTO = 0, DVH_FV_PER_IMAGE = 1, DVH_FV_NOT_TILED = 2, DVH_FV_BATCHED = 3, DVH_FV_TILED = 4 };
+int dvh_disp_fv_as(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const double* kgrid, double kmin,
+                   double kmax, const double* kq, int32_t nF, int32_t nV, const int32_t* fj, const double* fw,
+                   const double* sg, int32_t sgl, float* fv, int32_t form, int32_t images_per_block, void* stream);
+
+/* What dvh_disp_fv_as would launch for this shape, form and images_per_block: *form_out = DVH_FV_PER_IMAGE,
+ * DVH_FV_BATCHED or DVH_FV_TILED (where the chain ended) and *G_out its images per block (0 for the per-image
+ * kernel); both 0 when B <= 0 or nV <= 0 (nothing runs).  Host arithmetic only: no launch, no device.  The same
+ * status as dvh_disp_fv_as for the same arguments. */
+int dvh_disp_fv_pick(int32_t B, int32_t n_kb, int32_t n_fb, int32_t nF, int32_t nV, int32_t sgl, int32_t form,
+                     int32_t images_per_block, int32_t* form_out, int32_t* G_out);
 
 /* dvh_disp_fv for large batches with the FK cells staged per block: 256-thread blocks of 4 velocities x a
  * frequency tile (TO outputs, n_tile tiles, 12-sample halos; one tile when nF <= 256), block ct =
@@ -168,6 +195,14 @@ int dvh_disp_fv_cells(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, c
                       double kmax, const double* kq, int32_t nF, int32_t nV, const double* fw, const double* sg,
                       int32_t sgl, int32_t TO, int32_t n_tile, int32_t VT, int32_t max_cell, const int32_t* cell_off,
                       const int32_t* n_cell, const int32_t* qidx, float* fv, void* stream);
+
+/* dvh_disp_fv_cells with images_per_block > 0 images per block (0: the launcher's count, ~8 k blocks of at most
+ * 64 images, which is what dvh_disp_fv_cells passes). */
+int dvh_disp_fv_cells_as(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const double* kgrid, double kmin,
+                         double kmax, const double* kq, int32_t nF, int32_t nV, const double* fw, const double* sg,
+                         int32_t sgl, int32_t TO, int32_t n_tile, int32_t VT, int32_t max_cell,
+                         const int32_t* cell_off, const int32_t* n_cell, const int32_t* qidx, float* fv,
+                         int32_t images_per_block, void* stream);
 
 /* dvh_disp_fv with the Savitzky-Golay filter on the float64 matrix pipe (map_fv's savgol,
  * modules/utils.py:473): each (16 velocities x 16 frequencies) output tile is one banded GEMM of

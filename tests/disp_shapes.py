@@ -43,6 +43,31 @@ FULL_GRID = {64: dict(nk=128, K2=128, lds=101376), 65: dict(nk=256, K2=132, lds=
 RAGGED = dict(nch=200, nt=64, dx=3.0, nk=512, n_kb=193, n_fb=14, MT=208, K2=400)
 
 
+# The kernel selections the f-v sampling tests run: None = the product's choice, else (form, images_per_block) of
+# das_diff_veh_amd.disp.fv_choice.  "not_tiled" and "chain" name no kernel, they narrow the choice made by size.
+FV_MODES = [None, ("tiled", 0), ("not_tiled", 0), ("batched", 3), ("batched", 16), ("tiled", 3), ("per_image", 0),
+            ("cells", 3), ("chain", 0), ("mfma", 0), ("mfma", 3)]
+FV_FEW_IMAGES = {None: "per_image", "not_tiled": "per_image", "chain": "per_image"}  # a few small images, by size
+
+
+def fv_mode_kwargs(mode):
+    return {} if mode is None else dict(form=mode[0], images_per_block=mode[1])
+
+
+def check_fv_choice(plan, B, mode, by_size=FV_FEW_IMAGES, falls=()):
+    """fv_choice under ``mode`` names the kernel asked for, with the images per block asked for -- or, for a form
+    listed in ``falls`` (a structural condition of that kernel fails at this shape), the kernel named there; the
+    modes that name no kernel give ``by_size``'s.  Returns the kernel's name."""
+    from das_diff_veh_amd.disp import fv_choice
+    form, ipb = (None, 0) if mode is None else mode
+    name, G = fv_choice(plan, B, **fv_mode_kwargs(mode))
+    want = by_size[form] if form in by_size else dict(falls).get(form, form)
+    assert name == want, (mode, name, want)
+    if name == form and ipb:
+        assert G == ipb, (mode, G)
+    return name
+
+
 def axes(nF=47, nV=33):
     return np.linspace(1.0, 25.0, nF), np.linspace(200.0, 1200.0, nV)
 

@@ -292,9 +292,9 @@ def test_public_fk_full_grid(device, nch):
 
 
 @pytest.mark.parametrize("nch,nt", [(17, 257), (25, 31), (33, 499), (128, 500)])
-def test_tiled_contraction_equals_one_block_kernel(device, monkeypatch, nch, nt):
-    """DVH_FK_TILED=1 sends a table that fits one block through fk_contract_tiled_kernel: each bin is summed over the
-    channels in the same order, so |FK| is bitwise the one-block kernel's (plain and slot-accumulated, one gather
+def test_tiled_contraction_equals_one_block_kernel(device, nch, nt):
+    """contraction="tiled" sends a table that fits one block through fk_contract_tiled_kernel: each bin is summed over
+    the channels in the same order, so |FK| is bitwise the one-block kernel's (plain and slot-accumulated, one gather
     per slot)."""
     import torch
 
@@ -302,9 +302,11 @@ def test_tiled_contraction_equals_one_block_kernel(device, monkeypatch, nch, nt)
     plan = _plan(nch, nt)
     xd = torch.as_tensor(np.random.default_rng(nt).standard_normal((3, nch, nt)).astype(np.float32), device=device)
     kw = dict(slots=[2, 0, 1], weights=[1.0, 0.5, 2.0], n_slot=3)
-    one, one_s = fk_grid(xd, plan).cpu().numpy(), fk_grid(xd, plan, **kw).cpu().numpy()
-    monkeypatch.setenv("DVH_FK_TILED", "1")
-    til, til_s = fk_grid(xd, plan).cpu().numpy(), fk_grid(xd, plan, **kw).cpu().numpy()
+    assert ds.fk_lds_bytes(plan) <= ds.FK_LDS_LIMIT  # by size these tables take the one-block kernel
+    one = fk_grid(xd, plan, contraction="one_block").cpu().numpy()
+    one_s = fk_grid(xd, plan, contraction="one_block", **kw).cpu().numpy()
+    til = fk_grid(xd, plan, contraction="tiled").cpu().numpy()
+    til_s = fk_grid(xd, plan, contraction="tiled", **kw).cpu().numpy()
     assert np.array_equal(one, til)
     assert np.array_equal(one_s, til_s)
 
@@ -390,8 +392,15 @@ def test_fv_class_means_vs_oracle(device):
 
 
 # ------------------------------------------------------------------------------------------ (f) f-v maps by grid size
-MODES = [None, ("DVH_FV_TILE", "2"), ("DVH_FV_TILE", "0"), ("DVH_FV_G", "3"), ("DVH_FV_G", "16"), ("DVH_FV_TG", "3"),
-         ("DVH_FV_G", "0"), ("DVH_FV_CELLS", "1"), ("DVH_FV_CELLS", "0"), ("DVH_FV_MFMA", "1"), ("DVH_FV_MG", "3")]
+# forced kernels whose structural conditions fail at a geometry, and the kernel the choice ends at instead
+FV_FALLS = {
+    # 6 400 bins: above the 4 096 the batched kernel's threads prefetch
+    (33, 499): {"batched": "per_image"},
+    # 12 700 and 12 640 bins: 99 KB of |FK| against the tiled kernel's 64 KB of LDS, above the batched kernel's 4 096
+    # bins and the MFMA kernel's 8 192; the cell-staged kernel holds only the cells a block reads and still runs
+    (65, 500): {"tiled": "per_image", "batched": "per_image", "mfma": "per_image"},
+    (25, 2000): {"tiled": "per_image", "batched": "per_image", "mfma": "per_image"},
+}
 _FV_REF = {}
 
 
@@ -413,20 +422,6 @@ def _fv_case(nch, nt, B, nV, nF, device, norm=False, zero_row=None):
     return _FV_REF[key]
 
 
-def _set_mode(monkeypatch, mode):
-    if mode is None:
-        return
-    if mode[0] == "DVH_FV_G":
-        monkeypatch.setenv("DVH_FV_TILE", "0")
-    if mode[0] == "DVH_FV_TG":
-        monkeypatch.setenv("DVH_FV_TILE", "2")
-    if mode == ("DVH_FV_CELLS", "1"):
-        monkeypatch.setenv("DVH_FV_TG", "3")
-    if mode[0] == "DVH_FV_MG":
-        monkeypatch.setenv("DVH_FV_MFMA", "1")
-    monkeypatch.setenv(*mode)
-
-
 def _check_maps(got, refs):
     from oracle import disp as odisp
     worst = 0.0
@@ -438,18 +433,19 @@ def _check_maps(got, refs):
     return worst
 
 
-@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("mode", ds.FV_MODES)
 @pytest.mark.parametrize("B,nV,nF", [(3, 33, 47), (5, 70, 260)])
 @pytest.mark.parametrize("nch,nt", [(1, 500), (17, 257), (33, 499), (65, 500), (25, 2000)])
-def test_fv_maps_each_side_of_the_staging_limits(device, monkeypatch, nch, nt, B, nV, nF, mode):
+def test_fv_maps_each_side_of_the_staging_limits(device, nch, nt, B, nV, nF, mode):
     """fv_maps against oracle.map_fv with |FK| grids of 200, 3 200, 6 400 (above the batched kernel's 4 096), 12 700
     and 12 640 bins (above every staged kernel's limit: the per-image kernel) under every kernel selection of
-    tests/test_fv_batch_gpu.py; a forced kernel that does not apply falls back and still matches."""
+    tests/test_fv_batch_gpu.py; fv_choice names the forced kernel, or where it does not apply (FV_FALLS) the one it
+    falls back to, which still matches."""
     from das_diff_veh_amd.disp import fv_maps
     data, plan, refs = _fv_case(nch, nt, B, nV, nF, device)
-    _set_mode(monkeypatch, mode)
-    worst = _check_maps(fv_maps(data, plan).double().cpu().numpy(), refs)
-    print(f"fv_maps {nch} x {nt} ({B}, {nV}, {nF}) {mode}: rel-err {worst:.3g}")
+    name = ds.check_fv_choice(plan, B, mode, falls=FV_FALLS.get((nch, nt), ()))
+    worst = _check_maps(fv_maps(data, plan, **ds.fv_mode_kwargs(mode)).double().cpu().numpy(), refs)
+    print(f"fv_maps {nch} x {nt} ({B}, {nV}, {nF}) {mode} -> {name}: rel-err {worst:.3g}")
 
 
 @pytest.mark.parametrize("nch,nt", ds.TILED)

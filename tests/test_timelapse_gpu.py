@@ -20,26 +20,25 @@ DX, DT = 8.16, 0.003999999999997783
 def job(device):
     import torch
 
-    from das_diff_veh_amd.disp import DispPlan, _use_mfma, fk_grid
+    from das_diff_veh_amd.disp import DispPlan, fk_grid, fv_choice
     from das_diff_veh_amd.synth import synth_gathers
     freqs, vels = np.linspace(1.0, 25.0, NF), np.linspace(200.0, 1200.0, NV)
     plan = DispPlan(25, 500, DX, DT, freqs, vels)
-    assert _use_mfma(plan, B)
+    assert fv_choice(plan, B)[0] == "mfma"
     data = synth_gathers(B, 25, 500, DX, DT, device, seed=7)
     FK = fk_grid(data, plan)
     torch.cuda.synchronize()
     return dict(plan=plan, data=data, FK=FK, freqs=freqs, vels=vels)
 
 
-def test_mfma_fv_matches_valu_fv_on_the_full_batch(job, monkeypatch):
+def test_mfma_fv_matches_valu_fv_on_the_full_batch(job):
     import torch
 
-    from das_diff_veh_amd.disp import fv_from_fk
+    from das_diff_veh_amd.disp import fv_choice, fv_from_fk
     plan, FK = job["plan"], job["FK"]
     got = fv_from_fk(FK, plan)  # product dispatch: fv_mfma_kernel
-    monkeypatch.setenv("DVH_FV_MFMA", "0")
-    monkeypatch.setenv("DVH_FV_CELLS", "1")
-    ref = fv_from_fk(FK, plan)  # cell-staged fv_tile_kernel
+    assert fv_choice(plan, B, form="cells")[0] == "cells"
+    ref = fv_from_fk(FK, plan, form="cells")  # cell-staged fv_tile_kernel
     torch.cuda.synchronize()
     peak = ref.abs().amax(dim=(1, 2))
     rel = (got - ref).abs().amax(dim=(1, 2)) / peak

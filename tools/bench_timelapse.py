@@ -72,7 +72,7 @@ def main():
                   _lib.ptr(FK), None, None, 0, st)
         if ev:
             ev[2].record(stream)
-        fv_from_fk(FK, plan, out=fv)  # the product dispatch (cell-staged tiles for a batch this size)
+        fv_from_fk(FK, plan, out=fv)  # the product dispatch (fv_choice)
         if ev:
             ev[3].record(stream)
 
@@ -100,8 +100,8 @@ def main():
     tdft_flop = 2.0 * M * K * N
     fk_flop = 2.0 * B * (2 * plan.MT) * plan.K2 * plan.n_fb
     fv_bytes = 4.0 * B * plan.nV * plan.nF + 8.0 * B * plan.n_kb * plan.n_fb
-    from das_diff_veh_amd.disp import _use_mfma
-    mfma = _use_mfma(plan, B)
+    from das_diff_veh_amd.disp import fv_choice
+    mfma = fv_choice(plan, B)[0] == "mfma"
     fir_flop = 2.0 * 25 * B * plan.nV * plan.nF
     n_tiles = -(-(plan.nF - 16) // 16) + 1
     mfma_flop = 2.0 * 16 * 16 * 40 * n_tiles * B * -(-plan.nV // 16)
