@@ -7,7 +7,7 @@ Host side does only integer/float64 bookkeeping with the reference's own express
   FITPACK degree-1 basis h = (t_hi - q, q - t_lo) / (t_hi - t_lo)
   savgol_filter(25, 4, mode='interp') as a linear operator: interior taps (savgol_coeffs) and the
   two edge polynomial-fit matrices (_fit_edge)
-Every FLOP on the data runs in the kernels (das_diff_veh_amd/csrc/dvh_disp.hip).
+Every FLOP on the data runs in the kernels (das_diff_veh_amd/csrc/dvh_disp.hip, dvh_fv.hip).
 """
 from __future__ import annotations
 
@@ -129,13 +129,14 @@ class DispPlan:
         """Per (velocity chunk, frequency tile) block of dvh_disp_fv_cells: the FK cells its bilinear stencils
         read -- rows m, m + 1 of columns j, j + 1 for every (f, v) it samples -- column-major (each column's
         rows lo..hi contiguous), and per (f, v) the compact indices of (m, j) and (m, j + 1) with m.
-        Returns a dict of numpy tables (cached), or None when a block would not fit."""
+        Returns a dict of numpy tables (cached), or None when a block would not fit or the Savitzky-Golay window
+        reaches past the tile's halo (sg_window > 25)."""
         if self._cells is not None:
             return self._cells or None
         T, VT, pad = self.TILE_THREADS, self.TILE_VT, self.TILE_PAD
         nF, nV = self.nF, self.nV
         nt, TO = self.cell_tiles()
-        ok = nF >= self.sgl
+        ok = self.sgl <= min(nF, 2 * pad + 1)  # a tile's halo covers windows up to 25
         nvc = -(-nV // VT)
         n_ct = nvc * nt
         qidx = np.zeros((n_ct, T, VT, 4), dtype=np.int32)
@@ -198,12 +199,17 @@ class DispPlan:
             self._mfma = dict(hx=np.ascontiguousarray(hx), cb=np.ascontiguousarray(cb))
         return self._mfma
 
-    def tables(self, device):
-        key = str(device)
+    def tables(self, device, kind="base"):
+        """The plan's tables on ``device`` (uploaded once per device and kind): "base" the twiddles, contraction
+        matrix and query tables every launch reads, "mfma" mfma_tables(), "cells" cell_tables() (its integers as
+        they are, its arrays as tensors)."""
+        key = (kind, str(device))
         if key not in self._dev:
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
-            self._dev[key] = dict(wt=t(self.wt), atab=t(self.atab), kgrid=t(self.kgrid), kq=t(self.kq),
-                                  fj=t(self.fj), fw=t(self.fw), sg=t(self.sg))
+            host = {"base": lambda: dict(wt=self.wt, atab=self.atab, kgrid=self.kgrid, kq=self.kq, fj=self.fj,
+                                         fw=self.fw, sg=self.sg),
+                    "mfma": self.mfma_tables, "cells": self.cell_tables}[kind]()
+            self._dev[key] = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) if isinstance(v, np.ndarray)
+                              else v for k, v in host.items()}
         return self._dev[key]
 
 
@@ -258,20 +264,22 @@ _CHAIN_NAME = {1: "per_image", 3: "batched", 4: "tiled"}
 FORMS = (None, "mfma", "cells", "chain", *_CHAIN)
 
 
-def _fv_staged(plan: DispPlan, B: int, form):
-    """"mfma" or "cells" where one of the two table-fed kernels runs, None for the dvh_disp_fv chain."""
+def _fv_staged(plan: DispPlan, B: int, form, images_per_block=0):
+    """(name, G): "mfma" or "cells" where one of the two table-fed kernels runs, None for the dvh_disp_fv chain, and
+    the images per block to pass on -- the caller's where ``form`` names the kernel that runs, else 0."""
     if form not in FORMS:
         raise ValueError(f"form must be one of {FORMS}")
+    name = None
     # dvh_disp_fv_mfma: savgol window 25, nF >= 32, a compact FK grid of at most 8 192 bins
     mfma_ok = plan.sgl == 25 and plan.nF >= 32 and plan.n_kb * plan.n_fb <= 8192
-    if mfma_ok and (form == "mfma" or (form is None and B * -(-plan.nV // 64) >= MFMA_MIN_BLOCKS)):
-        return "mfma"
     # dvh_disp_fv_cells for batches that fill the chip; few images (the bench's class stacks) keep the chain
     n_blocks = B * plan.cell_tiles()[0] * -(-plan.nV // DispPlan.TILE_VT)
-    if form == "cells" or (form in (None, "mfma") and n_blocks >= CELLS_MIN_BLOCKS):
+    if mfma_ok and (form == "mfma" or (form is None and B * -(-plan.nV // 64) >= MFMA_MIN_BLOCKS)):
+        name = "mfma"
+    elif form == "cells" or (form in (None, "mfma") and n_blocks >= CELLS_MIN_BLOCKS):
         if plan.cell_tables() is not None:
-            return "cells"
-    return None
+            name = "cells"
+    return name, int(images_per_block) if name is not None and form == name else 0
 
 
 def fv_choice(plan: DispPlan, B: int, form=None, images_per_block=0):
@@ -280,12 +288,13 @@ def fv_choice(plan: DispPlan, B: int, form=None, images_per_block=0):
     form None is the product's choice: mfma from MFMA_MIN_BLOCKS blocks on, cells from CELLS_MIN_BLOCKS on, else the
     dvh_disp_fv chain (tiled, batched, per-image by size: dvh_disp_fv_pick).  A form named by the caller (FORMS;
     "chain" = dvh_disp_fv's own choice, "not_tiled" = batched or per-image by size) runs wherever the kernel's
-    structural conditions hold, whatever the batch size; where they do not, a refused "mfma" takes the product's
-    choice among the others and every other refused form the chain, down to per_image.  images_per_block > 0 sets G
-    of the kernel named by ``form``; G is 0 where the launcher counts for itself (mfma, cells) and for per_image."""
-    name = _fv_staged(plan, B, form)
+    structural conditions hold, whatever the batch size; where they do not (a Savitzky-Golay window other than 25
+    for mfma, above 25 for cells and tiled among them), a refused "mfma" takes the product's choice among the others
+    and every other refused form the chain, down to per_image.  images_per_block > 0 sets G of the kernel named by
+    ``form``; G is 0 where the launcher counts for itself (mfma, cells) and for per_image."""
+    name, G = _fv_staged(plan, B, form, images_per_block)
     if name is not None:
-        return name, int(images_per_block) if form == name else 0
+        return name, G
     f, g = C.c_int32(), C.c_int32()
     _lib.call("dvh_disp_fv_pick", B, plan.n_kb, plan.n_fb, plan.nF, plan.nV, plan.sgl, _CHAIN.get(form, 0),
               int(images_per_block), C.byref(f), C.byref(g))
@@ -294,7 +303,7 @@ def fv_choice(plan: DispPlan, B: int, form=None, images_per_block=0):
 
 def _use_mfma(plan: DispPlan, B: int) -> bool:
     """fv_choice(plan, B)[0] == "mfma", under the name bench.py imports."""
-    return _fv_staged(plan, B, None) == "mfma"
+    return _fv_staged(plan, B, None)[0] == "mfma"
 
 
 def fv_from_fk(FK, plan: DispPlan, out=None, form=None, images_per_block=0):
@@ -304,33 +313,22 @@ def fv_from_fk(FK, plan: DispPlan, out=None, form=None, images_per_block=0):
     B = FK.shape[0]
     if out is None:
         out = torch.empty((B, plan.nV, plan.nF), dtype=torch.float32, device=dev)
-    name = _fv_staged(plan, B, form)
-    G = int(images_per_block) if form == name else 0
+    name, G = _fv_staged(plan, B, form, images_per_block)
     if name == "mfma":
-        key = ("mfma", str(dev))
-        if key not in plan._dev:
-            mt = plan.mfma_tables()
-            plan._dev[key] = {k: torch.from_numpy(v).to(dev) for k, v in mt.items()}
-        mt = plan._dev[key]
+        mt = plan.tables(dev, "mfma")
         _lib.call("dvh_disp_fv_mfma", _lib.ptr(FK), B, plan.n_kb, plan.n_fb, _lib.ptr(mt["hx"]), _lib.ptr(mt["cb"]),
                   plan.nF, plan.nV, _lib.ptr(tb["fw"]), _lib.ptr(tb["sg"]), plan.sgl, G, _lib.ptr(out),
                   _lib.stream_of(dev))
-        return out
-    if name == "cells":
-        key = ("cells", str(dev))
-        if key not in plan._dev:
-            ct = plan.cell_tables()
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-            plan._dev[key] = dict(ct, cell_off=t(ct["cell_off"]), n_cell=t(ct["n_cell"]), qidx=t(ct["qidx"]))
-        c = plan._dev[key]
+    elif name == "cells":
+        c = plan.tables(dev, "cells")
         _lib.call("dvh_disp_fv_cells_as", _lib.ptr(FK), B, plan.n_kb, plan.n_fb, _lib.ptr(tb["kgrid"]), plan.kmin,
                   plan.kmax, _lib.ptr(tb["kq"]), plan.nF, plan.nV, _lib.ptr(tb["fw"]), _lib.ptr(tb["sg"]), plan.sgl,
                   c["TO"], c["n_tile"], DispPlan.TILE_VT, c["max_cell"], _lib.ptr(c["cell_off"]), _lib.ptr(c["n_cell"]),
                   _lib.ptr(c["qidx"]), _lib.ptr(out), G, _lib.stream_of(dev))
-        return out
-    _lib.call("dvh_disp_fv_as", _lib.ptr(FK), B, plan.n_kb, plan.n_fb, _lib.ptr(tb["kgrid"]), plan.kmin, plan.kmax,
-              _lib.ptr(tb["kq"]), plan.nF, plan.nV, _lib.ptr(tb["fj"]), _lib.ptr(tb["fw"]), _lib.ptr(tb["sg"]),
-              plan.sgl, _lib.ptr(out), _CHAIN.get(form, 0), int(images_per_block), _lib.stream_of(dev))
+    else:
+        _lib.call("dvh_disp_fv_as", _lib.ptr(FK), B, plan.n_kb, plan.n_fb, _lib.ptr(tb["kgrid"]), plan.kmin, plan.kmax,
+                  _lib.ptr(tb["kq"]), plan.nF, plan.nV, _lib.ptr(tb["fj"]), _lib.ptr(tb["fw"]), _lib.ptr(tb["sg"]),
+                  plan.sgl, _lib.ptr(out), _CHAIN.get(form, 0), int(images_per_block), _lib.stream_of(dev))
     return out
 
 

@@ -167,10 +167,12 @@ int dvh_disp_fv(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const d
 
 /* The three kernels behind dvh_disp_fv, all with the same outputs: per-image (one block per image and 4 velocities),
  * batched (G images per block share the per-(f, v) weights; nF <= 1024 and an FK grid of <= 4 096 bins) and
- * frequency-tiled (tiles of ~200 outputs, G images per block; the FK grid and the filter within 64 KB of LDS).
+ * frequency-tiled (tiles of ~200 outputs, G images per block; the FK grid and the filter within 64 KB of LDS, and
+ * sgl <= 25: a block samples 12 frequencies to either side of its tile, which is as far as the filter may reach).
  * dvh_disp_fv is dvh_disp_fv_as(..., DVH_FV_AUTO, 0): each kernel where it measured fastest.  A named form drops
  * the size thresholds of that choice, never a kernel's own limits: where the named kernel cannot run the chain
- * goes on as under AUTO, tiled -> batched -> per-image.  DVH_FV_NOT_TILED leaves the tiled kernel out and chooses
+ * goes on, tiled -> batched -> per-image (a refused DVH_FV_TILED still drops the batched kernel's size threshold;
+ * sgl = 27 named TILED runs batched).  DVH_FV_NOT_TILED leaves the tiled kernel out and chooses
  * between the other two by size.  images_per_block > 0 sets G of the named kernel (TILED, BATCHED); 0 is the
  * launcher's count. */
 enum { DVH_FV_AUTO = 0, DVH_FV_PER_IMAGE = 1, DVH_FV_NOT_TILED = 2, DVH_FV_BATCHED = 3, DVH_FV_TILED = 4 };
@@ -190,7 +192,9 @@ int dvh_disp_fv_pick(int32_t B, int32_t n_kb, int32_t n_fb, int32_t nF, int32_t 
  * chunk * n_tile + tile stages only the cells its bilinear stencils read: cell_off[ct][max_cell] (FK
  * offsets m * n_fb + j, column-major per column), n_cell[ct], and per (f, v) of the block
  * qidx[ct][256][4][4] int32 = {compact index of (m, j), of (m, j + 1), m, 0}, f = tile start - halo + thread.
- * Tables: das_diff_veh_amd.disp.DispPlan.cell_tables.  VT must be 4.  Same outputs as dvh_disp_fv. */
+ * Tables: das_diff_veh_amd.disp.DispPlan.cell_tables.  VT must be 4.  Same outputs as dvh_disp_fv.  -4 for
+ * sgl > 25 (the window reaches past the halo; cell_tables returns None for such a plan), for a tile wider than the
+ * block, or a last tile of fewer than 13 outputs. */
 int dvh_disp_fv_cells(const double* FK, int32_t B, int32_t n_kb, int32_t n_fb, const double* kgrid, double kmin,
                       double kmax, const double* kq, int32_t nF, int32_t nV, const double* fw, const double* sg,
                       int32_t sgl, int32_t TO, int32_t n_tile, int32_t VT, int32_t max_cell, const int32_t* cell_off,

@@ -50,7 +50,7 @@ def bilinear(fk_res, fft_f, fft_k, kq, fq):
     return (1 - a) * (1 - b) * z00 + a * (1 - b) * z10 + (1 - a) * b * z01 + a * b * z11
 
 
-def map_fv(data, dx, dt, freqs, vels, norm=False):
+def map_fv(data, dx, dt, freqs, vels, norm=False, sg_window=25):
     if norm:
         data = data / np.linalg.norm(data, axis=-1, keepdims=True, ord=1)
     res, fft_f, fft_k = fk(data, dx, dt)
@@ -58,7 +58,7 @@ def map_fv(data, dx, dt, freqs, vels, norm=False):
     ones = np.ones(len(vels))
     for i, fr in enumerate(freqs):
         fv[i, :] = bilinear(res, fft_f, fft_k, np.divide(ones * fr, vels), fr)
-    fv = scipy.signal.savgol_filter(fv, 25, 4, axis=0)
+    fv = scipy.signal.savgol_filter(fv, sg_window, 4, axis=0)  # the reference's window is 25
     return fv.T
 
 

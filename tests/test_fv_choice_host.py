@@ -116,6 +116,42 @@ def test_pick_above_the_staged_grid_sizes(lib):
         assert _pick(lib, 8192, 200, 4, form, **huge) == ("per_image", 0), form
 
 
+def test_window_each_side_of_the_tile_halo(lib):
+    """A tiled block samples 12 frequencies to either side of its tile, so the tiled kernels filter windows up to 25.
+    At 27 the chain goes on to the batched kernel, by size and when "tiled" is named (which keeps the batched kernel
+    named: 3 images run it too); DispPlan.cell_tables refuses the plan, so "cells" takes the chain's choice by size;
+    dvh_disp_fv_cells_as answers -4 before it touches its pointers."""
+    from das_diff_veh_amd.disp import DispPlan, fv_choice
+    for sgl in (5, 23, 25):
+        assert _pick(lib, 8192, 200, 4, sgl=sgl) == ("tiled", 1), sgl
+        assert _pick(lib, 3, 413, 9, "tiled", 3, sgl=sgl) == ("tiled", 3), sgl
+    assert _pick(lib, 8192, 200, 4, sgl=27) == ("batched", 8)
+    assert _pick(lib, 3, 413, 9, "tiled", 3, sgl=27) == ("batched", 1)
+    assert _pick(lib, 3, 47, 9, "tiled", 3, sgl=27) == ("batched", 1)
+    assert _pick(lib, 3, 413, 9, sgl=27) == ("per_image", 0)
+    mk = lambda w, nF=413: DispPlan(25, 500, DX, DT, np.linspace(1.0, 25.0, nF), np.linspace(200.0, 1200.0, 9),  # noqa: E731
+                                    sg_window=w)
+    for w in (5, 23, 25):
+        assert mk(w).cell_tables() is not None
+        assert fv_choice(mk(w), 3, "cells", 3) == ("cells", 3) and fv_choice(mk(w), 3, "tiled", 3) == ("tiled", 3)
+    wide = mk(27)
+    assert wide.cell_tables() is None
+    assert fv_choice(wide, 3, "cells", 3) == ("per_image", 0)
+    assert fv_choice(wide, 3, "tiled", 3) == ("batched", 1)
+    assert fv_choice(wide, 3, "batched", 3) == ("batched", 3) and fv_choice(wide, 3) == ("per_image", 0)
+    # 4 096 images are 36 864 cell blocks: cells by size at 23, the batched kernel (8 192 chunks over 1 024) at 27
+    assert fv_choice(mk(23), 4096) == ("cells", 0) and fv_choice(wide, 4096) == ("batched", 8)
+    ct = mk(25).cell_tables()
+    buf = np.zeros(16)
+    p = buf.ctypes.data_as(ctypes.c_void_p)
+    args = lambda sgl: (p, 3, 32, 100, p, 0.0, 1.0, p, 413, 9, p, p, sgl, ct["TO"], ct["n_tile"], 4, ct["max_cell"],  # noqa: E731
+                        p, p, p, p, 0, None)
+    with pytest.raises(ValueError, match="savgol window wider"):
+        lib.call("dvh_disp_fv_cells_as", *args(27))
+    with pytest.raises(ValueError, match="savgol window must be odd"):
+        lib.call("dvh_disp_fv_cells_as", *args(24))
+
+
 def test_pick_statuses(lib):
     """-4 (ValueError) for a window the kernels cannot filter and for more frequencies than the per-image kernel's
     160 KB of LDS hold (20 bytes each: 8 192); -2 for an unknown form; nothing to run reports form 0."""
