@@ -96,7 +96,7 @@ def _device_windows(windows, idx, mute_offset):
     ImagesFromWindows.get_images apis/imaging_classes.py:100-102; one dvh_mute_traj launch)."""
     from .. import _lib
     from ..device import to_device_f32
-    from ..preprocess import mute_traj_table
+    from ..preprocess import mute_traj_table, taper_on_device
     data = to_device_f32([windows[i].data for i in idx])
     mute = [k for k, i in enumerate(idx) if mute_offset is not None and not windows[i].muted_along_traj]
     if mute:
@@ -108,7 +108,7 @@ def _device_windows(windows, idx, mute_offset):
         sub = data if len(mute) == len(idx) else data[mute].contiguous()
         dev = sub.device
         tab_t = torch.from_numpy(np.ascontiguousarray(np.stack(tabs))).to(dev)
-        taper_t = torch.from_numpy(np.ascontiguousarray(taper, dtype=np.float64)).to(dev)
+        taper_t = taper_on_device(taper, dev)
         _lib.call("dvh_mute_traj", _lib.ptr(sub), 0, len(mute), sub.stride(0), sub.shape[1], sub.shape[2],
                   _lib.ptr(tab_t), _lib.ptr(taper_t), _lib.stream_of(dev))
         if sub is not data:

@@ -257,6 +257,8 @@ DVH_API int dvh_mute_traj(void* data, int32_t dtype, int32_t n_pass, int64_t pas
                           const int32_t* tab, const double* taper, void* stream) {
   if (!data || !tab || !taper) return set_error(-2, "null pointer argument");
   if (n_pass <= 0 || n_ch <= 0 || n_t <= 0) return 0;
+  if (n_ch > 65535 || n_pass > 65535)  // gridDim.y / gridDim.z limit
+    return set_error(-4, "too many channels or passes for one launch");
   const dim3 grid((n_t + 255) / 256, n_ch, n_pass);
   return with_float_type(dtype, [&](auto t) {
     using T = decltype(t);

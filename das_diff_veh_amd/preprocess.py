@@ -138,6 +138,14 @@ def mute_traj_table(x_axis, t_axis, veh_state_x, veh_state_t, offset=200, alpha=
     return np.stack([s, e, ts], axis=1).astype(np.int32), tukey(n_samp, alpha)
 
 
+def taper_on_device(taper, dev):
+    """The taper as a float64 device tensor.  An offset below one channel spacing gives an empty taper (every sample
+    is zeroed, as the reference does); the kernel then reads none of it but refuses a null pointer, which is what an
+    empty tensor has, so one unused entry stands in."""
+    taper = np.ascontiguousarray(taper, dtype=np.float64)
+    return torch.from_numpy(taper if taper.size else np.zeros(1)).to(dev)
+
+
 def mute_along_traj(window, offset=200, alpha=0.3, delta_x=20):
     tab, taper = mute_traj_table(window.x_axis, window.t_axis, window.veh_state_x, window.veh_state_t, offset, alpha,
                                  delta_x)
@@ -145,7 +153,7 @@ def mute_along_traj(window, offset=200, alpha=0.3, delta_x=20):
     n_ch, n_t = v.t.shape[-2], v.t.shape[-1]
     dev = v.t.device
     tab_t = torch.from_numpy(np.ascontiguousarray(tab)).to(dev)
-    taper_t = torch.from_numpy(np.ascontiguousarray(taper, dtype=np.float64)).to(dev)
+    taper_t = taper_on_device(taper, dev)
     _lib.call("dvh_mute_traj", _lib.ptr(v.t), v.dtype, 1, n_ch * n_t, n_ch, n_t, _lib.ptr(tab_t), _lib.ptr(taper_t),
               _lib.stream_of(dev))
     v.write_back()

@@ -292,7 +292,9 @@ int dvh_sosfiltfilt_planned(void* x, int32_t dtype, int64_t n_rows, int64_t row_
                             void* stream);
 
 /* SurfaceWaveWindow.mute_along_traj (apis/data_classes.py:49-72): tab[n_pass][n_t][3] =
- * {start, end, taper_start} per time sample; contiguous [n_ch][n_t] per pass. */
+ * {start, end, taper_start} per time sample; contiguous [n_ch][n_t] per pass, passes pass_stride elements
+ * apart.  One launch with a block row per (channel, pass): n_ch or n_pass above 65 535 returns -4 before
+ * anything is launched and the data is left as it was. */
 int dvh_mute_traj(void* data, int32_t dtype, int32_t n_pass, int64_t pass_stride, int32_t n_ch, int32_t n_t,
                   const int32_t* tab, const double* taper, void* stream);
 

@@ -52,9 +52,11 @@ def detect(data, t_axis, x_axis, start_x, detect_args=DEFAULT_DETECT, nx=15, sig
     return base, erode, lists
 
 
-def kf_track(peak_lists, x_sel, veh_base, sigma_a=0.01):
+def kf_track(peak_lists, x_sel, veh_base, sigma_a=0.01, trace=None):
     """The association and Kalman loop over the tracked rows' peak lists (positions x_sel) ->
-    veh_states [n_veh, n_steps], NaN or a peak index."""
+    veh_states [n_veh, n_steps], NaN or a peak index.  ``trace``, a [n_veh, n_steps] float64 array, receives the
+    float64 predicted arrival of every step that has one (the rest is left as it is); the result does not depend
+    on it."""
     n_veh, n_steps = len(veh_base), len(peak_lists)
     states = np.full((n_veh, n_steps), np.nan)
     T = np.zeros((n_veh, 2))       # filtered state: arrival sample, samples per metre
@@ -80,6 +82,8 @@ def kf_track(peak_lists, x_sel, veh_base, sigma_a=0.01):
                 Q = sigma_a * np.array([[0.25 * dx ** 4, 0.5 * dx ** 3], [0.5 * dx ** 3, dx ** 2]])
                 Tp[v] = A @ T[v]
                 Pp[v] = A @ P[v] @ A.T + Q
+                if trace is not None:
+                    trace[v, k] = Tp[v, 0]
                 base = int(Tp[v, 0])   # truncated toward zero, as the reference's integer array does
             dist = peaks - base
             ahead = dist[(dist > 0) & (dist <= AHEAD)]
