@@ -166,7 +166,7 @@ class VirtualShotGathersFromWindows(ImagesFromWindows):
 _log = logging.getLogger(__name__)
 
 
-def save_disp_imgs(windows, weight, min_win, x, start_x, end_x, offset, fig_dir):
+def save_disp_imgs(windows, weight, min_win, x, start_x, end_x, offset, fig_dir, transform="fk"):
     """apis/imaging_classes.py:50-85 (imaging_diff_{speed,weight}.ipynb#cell21): the class stack of a random
     subset of min_win windows and its dispersion image.
 
@@ -179,7 +179,11 @@ def save_disp_imgs(windows, weight, min_win, x, start_x, end_x, offset, fig_dir)
     ``avg_image.XCF_out`` / ``avg_image.disp.fv_map``) and the draw as ``images_all.sel_idx``, attributes the
     reference does not have.  Not done (plotting is outside the accelerated path): the figures the reference
     writes under ``fig_dir/x/`` (plot_image of the stack, plot_fv_map with and without normalisation) and the
-    CLAHE enhancement (fv_map_enhance, cv2), whose result the reference only passes to a commented-out plot."""
+    CLAHE enhancement (fv_map_enhance, cv2), whose result the reference only passes to a commented-out plot.
+    ``transform`` is compute_disp_image's: "fk" (map_fv) or "slant" (the phase-shift transform); another value raises
+    ValueError before the draw and before any device work."""
+    from ..bootstrap import check_transform
+    check_transform(transform)
     image_from_window_cls = VirtualShotGathersFromWindows
     sel_idx = random.sample(range(len(windows)), min_win)
     images_all = image_from_window_cls(windows)
@@ -189,30 +193,38 @@ def save_disp_imgs(windows, weight, min_win, x, start_x, end_x, offset, fig_dir)
     _log.info("save_disp_imgs: figures sg_%s_cars.pdf / disp_%s_cars_no_norm.pdf / disp_%s_cars_no_enhance.pdf under "
               "%s/%s/ are not written (plotting is outside the accelerated path; plot images.selected.avg_image with "
               "the reference's plot_xcorr / plot_fv_map)", weight, weight, weight, fig_dir, x)
-    _images.avg_image.compute_disp_image(end_x=0, start_x=-offset)
+    _images.avg_image.compute_disp_image(end_x=0, start_x=-offset, transform=transform)
     images_all.selected, images_all.sel_idx = _images, sel_idx
     return images_all
 
 
 def bootstrap_disp(surf_wins, bt_size, bt_times, sigma, pivot, start_x, end_x, ref_freq_idx, freq_lb, freq_up,
-                   ref_vel):
+                   ref_vel, transform="fk", walk=None):
     """apis/imaging_classes.py:8-48: bt_times resamples of random.sample(range(1, n), bt_size)
     windows -> class-stack VSG -> compute_disp_image(end_x=0, start_x=-150) -> one ridge per mode.
     Same draws (Python ``random``), same return value: (ridge_vel[mode][resample], freqs).  All
-    resamples run as one batch on the device (das_diff_veh_amd.bootstrap)."""
+    resamples run as one batch on the device (das_diff_veh_amd.bootstrap).  ``transform`` selects the image the ridges
+    are walked on: "fk" (map_fv, the reference's) or "slant" (the phase-shift transform, compute_disp_image(...,
+    transform="slant")); with "slant", ``walk`` = "fused" / "image" selects the kernel (bootstrap.bootstrap_ridges; the
+    results are the same).  A pair that does not exist raises ValueError before any device work."""
     from .. import bootstrap as bt
+    bt.check_transform(transform, walk)
     cache = bt.GatherCache(surf_wins, pivot, start_x, end_x)
     sels = bt.draw(len(surf_wins), bt_size, bt_times)
-    per_mode = bt.bootstrap_ridges(cache, sels, sigma, ref_freq_idx, freq_lb, freq_up, ref_vel)
+    per_mode = bt.bootstrap_ridges(cache, sels, sigma, ref_freq_idx, freq_lb, freq_up, ref_vel, transform=transform,
+                                   walk=walk)
     return [list(r) for r in per_mode], bt.FREQS.copy()
 
 
 def convergence_test(max_sample_num, windows, bt_times, sigma, x0, start_x, end_x, ref_freq_idx, freq_lb, freq_ub,
-                     vel_ref):
+                     vel_ref, transform="fk", walk=None):
     """imaging_diff_speed.ipynb#cell30: for bt_size = 1..max_sample_num, the summed per-frequency
     std of the bootstrap ridges -> [n_modes, max_sample_num].  The gathers are computed once for all
     60 x bt_times resamples (the notebook recomputes them per resample); draws as the notebook's; all
-    resamples imaged in one batch (das_diff_veh_amd.bootstrap.convergence)."""
+    resamples imaged in one batch (das_diff_veh_amd.bootstrap.convergence).  ``transform`` and ``walk`` as
+    bootstrap_disp takes them."""
     from .. import bootstrap as bt
+    bt.check_transform(transform, walk)
     cache = bt.GatherCache(windows, x0, start_x, end_x)
-    return bt.convergence(cache, max_sample_num, bt_times, sigma, ref_freq_idx, freq_lb, freq_ub, vel_ref)
+    return bt.convergence(cache, max_sample_num, bt_times, sigma, ref_freq_idx, freq_lb, freq_ub, vel_ref,
+                          transform=transform, walk=walk)

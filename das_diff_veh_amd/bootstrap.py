@@ -12,6 +12,11 @@ The reference recomputes every virtual shot gather of every resample from scratc
   4. every (resample, mode) ridge is walked by one wave (``dvh_ridge``): extract_ridge_ref_idx,
      modules/utils.py:621-678, with its strict velocity window, first-index argmax and savgol(25, 2).
 
+``transform="slant"`` makes the same statistics on the phase-shift image (Dispersion(transform="slant")) instead of
+the f-k image: either through the resamples' images and ``dvh_ridge`` (walk="image"), or, with the same results,
+through ``dvh_slant_ridge`` (walk="fused"), whose walk computes the steering sums of the velocities it compares from
+the stacks' spectra and forms no image (``plan_ridges``, ``slant_ridges``).
+
 Random draws use Python's ``random`` exactly as the reference does (``random.sample(range(1, n), k)``,
 index 0 never drawn), so seeding ``random`` reproduces the reference's resamples.
 """
@@ -25,7 +30,7 @@ import torch
 
 from . import _lib
 from .device import default_device, to_device_f32
-from .disp import DispPlan, fk_grid, fv_from_fk, savgol_operator
+from .disp import DispPlan, SlantPlan, _slant_spectra, fk_grid, fv_from_fk, savgol_operator, slant_maps
 from .plan import VsgParams, VsgPlan, pass_geometry
 from .vsg import vsg_gathers
 
@@ -61,6 +66,27 @@ def ridges_finish(pending):
     return (out.cpu().numpy(), picks.cpu().numpy()) if picks is not None else out.cpu().numpy()
 
 
+def _walk_band(freqs, freq_lb, freq_ub, ref_freq_idx, ref_vel):
+    """A walk's band lb <= f < ub as (first column c0, length nb), the kernels' reference index and the reference
+    velocities over the band (or None)."""
+    band = np.flatnonzero((freqs >= freq_lb) & (freqs < freq_ub))
+    if band.size == 0:
+        raise ValueError("empty frequency band")
+    if not np.array_equal(band, np.arange(band[0], band[-1] + 1)):
+        raise ValueError("the frequency band must be contiguous")
+    c0, nb = int(band[0]), int(band.size)
+    vr = None
+    if ref_freq_idx is not None and ref_vel is not None:
+        vr = ref_vel(freqs[band]) if callable(ref_vel) else np.asarray(ref_vel, dtype=np.float64)
+        vr = np.asarray(vr, dtype=np.float64).reshape(nb)
+    # ref_freq_idx=None -> vel_max mode (INT32_MIN); a negative index is a Python index into the band,
+    # walked in the reference's loop order (modules/utils.py:662-671)
+    ref = -2 ** 31 if ref_freq_idx is None else int(ref_freq_idx)
+    if ref_freq_idx is not None and not -nb <= ref < nb:
+        raise IndexError(f"index {ref} is out of bounds for axis 0 with size {nb}")
+    return c0, nb, ref, vr
+
+
 def ridges_launch(fv, freqs, vels, freq_lb, freq_ub, ref_freq_idx=None, sigma=25, vel_max=400, ref_vel=None,
                   return_picks=False):
     """The dvh_ridge launch of ridges() without the synchronising read-back: (out, status, picks) device
@@ -74,23 +100,9 @@ def ridges_launch(fv, freqs, vels, freq_lb, freq_ub, ref_freq_idx=None, sigma=25
         raise ValueError("fv shape does not match (vels, freqs)")
     if vel_desc.size > 1 and not np.all(np.diff(vel_desc) < 0):
         raise ValueError("the device ridge walk needs strictly increasing vels")
-    band = np.flatnonzero((freqs >= freq_lb) & (freqs < freq_ub))
-    if band.size == 0:
-        raise ValueError("empty frequency band")
-    if not np.array_equal(band, np.arange(band[0], band[-1] + 1)):
-        raise ValueError("the frequency band must be contiguous")
-    c0, nb = int(band[0]), int(band.size)
+    c0, nb, ref, vr = _walk_band(freqs, freq_lb, freq_ub, ref_freq_idx, ref_vel)
     dev = fv.device
     from .device import upload
-    vr = None
-    if ref_freq_idx is not None and ref_vel is not None:
-        vr = ref_vel(freqs[band]) if callable(ref_vel) else np.asarray(ref_vel, dtype=np.float64)
-        vr = np.asarray(vr, dtype=np.float64).reshape(nb)
-    # ref_freq_idx=None -> vel_max mode (INT32_MIN); a negative index is a Python index into the band,
-    # walked in the reference's loop order (modules/utils.py:662-671)
-    ref = -2 ** 31 if ref_freq_idx is None else int(ref_freq_idx)
-    if ref_freq_idx is not None and not -nb <= ref < nb:
-        raise IndexError(f"index {ref} is out of bounds for axis 0 with size {nb}")
     B = fv.shape[0]
     out = torch.empty((B, nb), dtype=torch.float64, device=dev)
     status = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -106,7 +118,24 @@ def ridges_launch(fv, freqs, vels, freq_lb, freq_ub, ref_freq_idx=None, sigma=25
 
 
 _DISP_PLANS = {}  # (nch, w, dt, freqs, vels) -> DispPlan, shared by GatherCache instances
+_SLANT_PLANS = {}  # the same key -> SlantPlan over all rows, velocities descending
 _STREAMS = {}
+TRANSFORMS = ("fk", "slant")
+SLANT_WALK = "fused"  # walk=None with transform="slant" (measured: tools/bench_boot_slant.py, profiles/boot_slant.json)
+
+
+def check_transform(transform, walk=None):
+    """The walk of a (transform, walk) pair -- "image": form the f-v images, then dvh_ridge; "fused": dvh_slant_ridge
+    on the spectra -- or ValueError for a pair that does not exist.  No device work."""
+    if transform not in TRANSFORMS:
+        raise ValueError(f"transform must be 'fk' or 'slant', not {transform!r}")
+    if transform == "fk":
+        if walk not in (None, "image"):
+            raise ValueError(f"transform='fk' samples a grid: walk must be None or 'image', not {walk!r}")
+        return "image"
+    if walk not in (None, "fused", "image"):
+        raise ValueError(f"walk must be None, 'fused' or 'image', not {walk!r}")
+    return SLANT_WALK if walk is None else walk
 
 
 def _side_stream(device, k):
@@ -208,19 +237,52 @@ class GatherCache:
             self._disp[key] = (s, e, _DISP_PLANS[pkey])
         return self._disp[key]
 
-    def images_of(self, stacks, first, start_x=-150, end_x=0):
-        """f-v images [B, Nvel, Nfreq] of resample stacks [B, nch, W] whose first drawn passes are ``first``: each
-        on its first pass's lag axis (its width w and time step)."""
+    def slant_plan(self, start_x=-150, end_x=0, freqs=FREQS, vels=VELS, w=None):
+        """disp_plan's channel slice with the SlantPlan of compute_disp_image(..., transform="slant") for a stack of
+        lag length w: all rows of the slice, velocities in descending order, dx = 8.16."""
+        w = int(self.w_of[0]) if w is None else int(w)
+        s = int(np.abs(self.gx - start_x).argmin())
+        e = int(np.abs(self.gx - end_x).argmin())
+        key = ("slant", s, e, id(freqs), id(vels), w)
+        if key not in self._disp:
+            gt = self._gt_of[w]
+            dt = float(gt[1] - gt[0])
+            nch = e + 1 - s
+            vel_desc = np.sort(np.asarray(vels, dtype=np.float64))[::-1]
+            pkey = (nch, w, dt, np.asarray(freqs, dtype=np.float64).tobytes(), vel_desc.tobytes())
+            if pkey not in _SLANT_PLANS:
+                if len(_SLANT_PLANS) >= 16:
+                    _SLANT_PLANS.pop(next(iter(_SLANT_PLANS)))
+                _SLANT_PLANS[pkey] = SlantPlan(nch, w, 8.16, dt, freqs, vel_desc, rows=(0, nch))
+            self._disp[key] = (s, e, _SLANT_PLANS[pkey])
+        return self._disp[key]
+
+    def _by_lag_length(self, first):
+        """The resamples grouped by the lag length of their first drawn pass: [(w, rows or None)], rows None when
+        every resample has the cache's width (one group, no gather of the stacks)."""
         wf = self.w_of[np.asarray(first, dtype=np.int64)]
         if np.all(wf == self.W):
-            _, _, plan = self.disp_plan(start_x, end_x, w=self.W)
-            return fv_from_fk(fk_grid(stacks, plan), plan)
+            return [(self.W, None)]
+        return [(int(w), np.flatnonzero(wf == w)) for w in np.unique(wf)]
+
+    def images_of(self, stacks, first, start_x=-150, end_x=0, transform="fk"):
+        """f-v images [B, Nvel, Nfreq] of resample stacks [B, nch, W] whose first drawn passes are ``first``: each
+        on its first pass's lag axis (its width w and time step).  ``transform``: "fk" (map_fv) or "slant" (the
+        phase-shift transform over all rows, rows in descending velocity)."""
+        check_transform(transform)
+
+        def image(stk, w):
+            if transform == "slant":
+                return slant_maps(stk, self.slant_plan(start_x, end_x, w=w)[2], norm=False)
+            plan = self.disp_plan(start_x, end_x, w=w)[2]
+            return fv_from_fk(fk_grid(stk, plan), plan)
+        groups = self._by_lag_length(first)
+        if groups[0][1] is None:
+            return image(stacks, self.W)
         out = None
-        for w in np.unique(wf):
-            rows = np.flatnonzero(wf == w)
-            _, _, plan = self.disp_plan(start_x, end_x, w=int(w))
+        for w, rows in groups:
             rt = torch.as_tensor(rows, device=self.device)
-            fv = fv_from_fk(fk_grid(stacks[rt][:, :, :int(w)], plan), plan)
+            fv = image(stacks[rt][:, :, :w], w)
             if out is None:
                 out = torch.empty((stacks.shape[0],) + tuple(fv.shape[1:]), dtype=fv.dtype, device=fv.device)
             out[rt] = fv
@@ -273,33 +335,153 @@ class GatherCache:
                   B, _lib.ptr(out), rows, _lib.stream_of(self.device))
         return out
 
-    def resample_images(self, sel, start_x=-150, end_x=0):
-        """f-v images [B, Nvel, Nfreq] of every draw's stack (compute_disp_image(end_x, start_x))."""
+    def resample_images(self, sel, start_x=-150, end_x=0, transform="fk"):
+        """f-v images [B, Nvel, Nfreq] of every draw's stack (compute_disp_image(end_x, start_x, transform))."""
+        check_transform(transform)
         sel = np.asarray(sel, dtype=np.int32)
-        return self.images_of(self.resample_stacks(sel, start_x, end_x), sel[:, 0], start_x, end_x)
+        return self.images_of(self.resample_stacks(sel, start_x, end_x), sel[:, 0], start_x, end_x, transform)
+
+
+def plan_ridges(stacks, plan: SlantPlan, freq_lb, freq_ub, ref_freq_idx, sigma, vel_max, ref_vel,
+                return_picks=False):
+    """ridges() of every mode on the phase-shift images slant_maps(stacks, plan, norm=False) would give, without the
+    images: the walk computes the values it compares (dvh_slant_ridge), each equal bit for bit to the image's, so
+    picks and ridges are those of ridges(slant_maps(...), plan.freqs, plan.vels[::-1], ...).  ``plan``: velocities
+    in descending order.  freq_lb, freq_ub, ref_freq_idx (an index into the band, or None), sigma and ref_vel are
+    sequences over the modes.  Returns the list over modes of ridges()'s results."""
+    return slant_ridges_finish(plan_ridges_launch(stacks, plan, freq_lb, freq_ub, ref_freq_idx, sigma, vel_max,
+                                                  ref_vel, return_picks))
+
+
+def plan_ridges_launch(stacks, plan: SlantPlan, freq_lb, freq_ub, ref_freq_idx, sigma, vel_max, ref_vel,
+                       return_picks=False, side_streams=False):
+    """The launches of plan_ridges() without the read-back: per mode (out, status, picks) device tensors for
+    ridges_finish.  The stacks' spectra are formed once (dvh_disp_tdft) and shared by the modes; the image tensor is
+    never allocated.  side_streams=True queues each mode's walk on a stream of its own, as convergence() does."""
+    from .device import upload
+    if plan.nV > 1 and not np.all(np.diff(plan.vels) < 0):
+        raise ValueError("the fused ridge walk needs a plan with strictly descending vels")
+    n_mode = len(freq_lb)
+    bands = [_walk_band(plan.freqs, freq_lb[m], freq_ub[m], ref_freq_idx[m], ref_vel[m]) for m in range(n_mode)]
+    D = _slant_spectra(stacks, plan, False)
+    dev, B = stacks.device, stacks.shape[0]
+    n_row = 0 if D is None else plan.n_row
+    if D is None:
+        D = torch.empty(2, dtype=torch.float64, device=dev)  # never read: the sums have no rows
+    tb = plan.tables(dev)
+    tabs = upload([np.asarray(_sg_ridge(), dtype=np.float64)] + [b[3] for b in bands if b[3] is not None], dev)
+    sg, rest = tabs[0], iter(tabs[1:])
+    vref = [next(rest) if b[3] is not None else None for b in bands]
+
+    def launch(m):
+        c0, nb, ref, _ = bands[m]
+        out = torch.empty((B, nb), dtype=torch.float64, device=dev)
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+        picks = torch.empty((B, nb), dtype=torch.float64, device=dev) if return_picks else None
+        _lib.call("dvh_slant_ridge", _lib.ptr(D), B, n_row, max(plan.n_fb, 1), _lib.ptr(tb["fb"]),
+                  _lib.ptr(tb["freqs"]), plan.nF, plan.dx, c0, nb, _lib.ptr(tb["vels"]), plan.nV, ref,
+                  float(sigma[m]), float(vel_max), _lib.ptr(vref[m]), _lib.ptr(sg), 25, _lib.ptr(out),
+                  _lib.ptr(status), _lib.ptr(picks), _lib.stream_of(dev))
+        return out, status, picks
+    if side_streams:
+        return _on_side_streams(dev, n_mode, launch, [D, sg] + [v for v in vref if v is not None])
+    return [launch(m) for m in range(n_mode)]
+
+
+def slant_ridges(cache: GatherCache, stacks, first, freq_lb, freq_ub, ref_freq_idx, sigma, vel_max, ref_vel,
+                 start_x=-150, end_x=0, return_picks=False):
+    """plan_ridges() for the resample stacks [B, nch, W] of a gather cache whose first drawn passes are ``first``:
+    each on its first pass's lag axis, as images_of(..., transform="slant") images them."""
+    return slant_ridges_finish(slant_ridges_launch(cache, stacks, first, freq_lb, freq_ub, ref_freq_idx, sigma,
+                                                   vel_max, ref_vel, start_x, end_x, return_picks))
+
+
+def slant_ridges_finish(pending):
+    """Host results of a slant_ridges_launch / plan_ridges_launch, mode by mode (synchronises; raises as
+    ridges_finish does)."""
+    return [ridges_finish(p) for p in pending]
+
+
+def slant_ridges_launch(cache: GatherCache, stacks, first, freq_lb, freq_ub, ref_freq_idx, sigma, vel_max, ref_vel,
+                        start_x=-150, end_x=0, return_picks=False, side_streams=False):
+    """The launches of slant_ridges() without the read-back.  A cache of one lag length is one plan_ridges_launch;
+    a mixed one walks each length's resamples with that length's plan and puts the results back in draw order."""
+    args = (freq_lb, freq_ub, ref_freq_idx, sigma, vel_max, ref_vel, return_picks, side_streams)
+    groups = cache._by_lag_length(first)
+    if groups[0][1] is None:
+        return plan_ridges_launch(stacks, cache.slant_plan(start_x, end_x, w=cache.W)[2], *args)
+    pend = None
+    for w, rows in groups:
+        rt = torch.as_tensor(rows, device=cache.device)
+        part = plan_ridges_launch(stacks[rt][:, :, :w], cache.slant_plan(start_x, end_x, w=w)[2], *args)
+        if pend is None:
+            pend = [tuple(None if t is None else torch.empty((stacks.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype,
+                                                             device=t.device) for t in p) for p in part]
+        for full, got in zip(pend, part):
+            for f, g in zip(full, got):
+                if f is not None:
+                    f[rt] = g
+    return pend
+
+
+def _on_side_streams(device, n, launch, inputs):
+    """launch(k) for k < n, each on the device's k-th side stream after the work queued so far on the current stream,
+    which then waits for all of them.  ``inputs``: the tensors the launches read; launch(k) returns the tensors it
+    writes (or None entries)."""
+    main = torch.cuda.current_stream(device)
+    ready = torch.cuda.Event()
+    ready.record(main)
+    out = []
+    for k in range(n):
+        st = _side_stream(device, k)
+        st.wait_event(ready)
+        with torch.cuda.stream(st):
+            out.append(launch(k))
+            for t in out[-1]:
+                if t is not None:
+                    t.record_stream(main)
+        for t in inputs:
+            t.record_stream(st)
+        main.wait_stream(st)
+    return out
+
+
+def _band_ref(ref_freq_idx, freq_lb):
+    """bootstrap_disp's ref_freq_idx (an index into FREQS) as an index into the band that starts at freq_lb."""
+    return ref_freq_idx - int(np.sum(FREQS < freq_lb))
 
 
 def bootstrap_ridges(cache: GatherCache, sels, sigma, ref_freq_idx, freq_lb, freq_up, ref_vel, start_x=-150,
-                     end_x=0):
-    """Ridge velocities per mode for draws ``sels`` [B, k]: list over modes of [B, n_band] arrays."""
-    fv = cache.resample_images(sels, start_x, end_x)
+                     end_x=0, transform="fk", walk=None):
+    """Ridge velocities per mode for draws ``sels`` [B, k]: list over modes of [B, n_band] arrays.  ``transform``
+    selects the image the ridges are walked on ("fk": map_fv, "slant": the phase-shift transform); with "slant",
+    ``walk`` selects how: "image" forms the images and walks them (dvh_ridge), "fused" computes the compared values
+    inside the walk (dvh_slant_ridge) with the same results, None takes SLANT_WALK."""
+    walk = check_transform(transform, walk)
+    if walk == "fused":
+        sels = np.asarray(sels, dtype=np.int32)
+        refs = [_band_ref(ref_freq_idx[m], freq_lb[m]) for m in range(len(freq_lb))]
+        return slant_ridges(cache, cache.resample_stacks(sels, start_x, end_x), sels[:, 0], freq_lb, freq_up, refs,
+                            sigma, 800, ref_vel, start_x, end_x)
+    fv = cache.resample_images(sels, start_x, end_x, transform)
     out = []
     for m in range(len(freq_lb)):
-        ref = ref_freq_idx[m] - int(np.sum(FREQS < freq_lb[m]))
-        out.append(ridges(fv, FREQS, VELS, freq_lb[m], freq_up[m], ref_freq_idx=ref, sigma=sigma[m], vel_max=800,
-                          ref_vel=ref_vel[m]))
+        out.append(ridges(fv, FREQS, VELS, freq_lb[m], freq_up[m], ref_freq_idx=_band_ref(ref_freq_idx[m], freq_lb[m]),
+                          sigma=sigma[m], vel_max=800, ref_vel=ref_vel[m]))
     return out
 
 
 def convergence(cache: GatherCache, max_size, bt_times, sigma, ref_freq_idx, freq_lb, freq_up, ref_vel, start_x=-150,
-                end_x=0, rand=random, phases=None):
+                end_x=0, rand=random, phases=None, transform="fk", walk=None):
     """The notebooks' convergence_test (imaging_diff_speed.ipynb#cell30) on a gather cache: for bt_size =
     1..max_size, bt_times resamples (the same random.sample draws in the same order as the notebook's
     per-size bootstrap_disp calls), their ridges per mode, and the summed per-frequency std -> [n_modes,
     max_size].  All max_size x bt_times resamples go through ONE dispersion batch (select_mean per size
     into one buffer, one tdft / fk / f-v launch each, one ridge launch per mode), so the host synchronises
     once per mode instead of once per (size, mode).  ``phases`` (optional dict) receives torch events
-    around the resample / dispersion / ridge parts for timing."""
+    around the resample / dispersion / ridge parts for timing.  ``transform`` and ``walk`` as bootstrap_ridges takes
+    them; the fused walk forms no images (its "disp1" event follows "select1" at once)."""
+    walk = check_transform(transform, walk)
     t_draw = time.perf_counter()
     sels = draw_sizes(cache.n, range(1, max_size + 1), bt_times, rand)
     if phases is not None:
@@ -310,27 +492,21 @@ def convergence(cache: GatherCache, max_size, bt_times, sigma, ref_freq_idx, fre
     ev("select0")
     stacks = cache.resample_stacks_sizes(sels, start_x, end_x)
     ev("select1")
-    fv = cache.images_of(stacks, np.concatenate([x[:, 0] for x in sels]), start_x, end_x)
-    ev("disp1")
+    first = np.concatenate([x[:, 0] for x in sels])
+    refs = [_band_ref(ref_freq_idx[m], freq_lb[m]) for m in range(len(freq_lb))]
     out = np.empty((len(freq_lb), max_size))
     # every mode's walk queued at once, each on its own stream: one walk is one wave per resample (1 800 waves,
     # a fraction of the chip), so the modes run side by side; one wait below
-    main = torch.cuda.current_stream(cache.device)
-    ready = torch.cuda.Event()
-    ready.record(main)
-    pend = []
-    for m in range(len(freq_lb)):
-        st = _side_stream(cache.device, m)
-        st.wait_event(ready)
-        with torch.cuda.stream(st):
-            pend.append(ridges_launch(fv, FREQS, VELS, freq_lb[m], freq_up[m], ref_freq_idx=ref_freq_idx[m] -
-                                      int(np.sum(FREQS < freq_lb[m])), sigma=sigma[m], vel_max=800,
-                                      ref_vel=ref_vel[m]))
-            for t in pend[-1]:
-                if t is not None:
-                    t.record_stream(main)
-        fv.record_stream(st)
-        main.wait_stream(st)
+    if walk == "fused":
+        ev("disp1")
+        pend = slant_ridges_launch(cache, stacks, first, freq_lb, freq_up, refs, sigma, 800, ref_vel, start_x, end_x,
+                                   side_streams=True)
+    else:
+        fv = cache.images_of(stacks, first, start_x, end_x, transform)
+        ev("disp1")
+        pend = _on_side_streams(cache.device, len(freq_lb), lambda m: ridges_launch(
+            fv, FREQS, VELS, freq_lb[m], freq_up[m], ref_freq_idx=refs[m], sigma=sigma[m], vel_max=800,
+            ref_vel=ref_vel[m]), [fv])
     ev("ridge1")
     for m, pd in enumerate(pend):
         r = np.asarray(ridges_finish(pd))

@@ -14,6 +14,7 @@
 
 #include "dvh_common.h"
 #include "dvh.h"
+#include "ridge_walk.h"
 
 namespace dvh {
 
@@ -86,96 +87,6 @@ __global__ __launch_bounds__(256) void select_mean_var_kernel(const float* __res
                   select_vec(G, pass_stride, K, out, out_stride));
 }
 
-// np.argmax order over (value, row): a NaN beats any number, the first row wins ties
-__device__ __forceinline__ bool better(float a, int ra, float b, int rb) {
-  const bool na = isnan(a), nb = isnan(b);
-  if (na != nb) return na;
-  if (na || a == b) return ra < rb;
-  return a > b;
-}
-
-__device__ __forceinline__ void wave_argmax(float& v, int& r) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v2 = __shfl_xor(v, o);
-    const int r2 = __shfl_xor(r, o);
-    if (r2 >= 0 && (r < 0 || better(v2, r2, v, r))) {
-      v = v2;
-      r = r2;
-    }
-  }
-}
-
-// first row r (of nV, velocities descending) with vel[r] < x: rows [0, r) have vel >= x
-__device__ __forceinline__ int first_below(const double* __restrict__ vel, int nV, double x) {
-  int lo = 0, hi = nV;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (vel[mid] < x) hi = mid;
-    else lo = mid + 1;
-  }
-  return lo;
-}
-
-// first row r with vel[r] <= x
-__device__ __forceinline__ int first_at_or_below(const double* __restrict__ vel, int nV, double x) {
-  int lo = 0, hi = nV;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (vel[mid] <= x) hi = mid;
-    else lo = mid + 1;
-  }
-  return lo;
-}
-
-// The velocity axis of a walk held in the wave's registers (nV <= 1024: lane l holds rows l S .. l S + S - 1,
-// S = ceil(nV / 64)), so that each step's two window bounds and its pick's velocity cost no memory round trip (the
-// binary searches over vel[] were 2 x 10 dependent loads per step, the walk's critical path).  Same results as
-// first_below / first_at_or_below / vel[r] on a descending axis; larger axes use those.
-struct VelAxis {
-  static constexpr int kMaxS = 16;
-  const double* vel;
-  int nV, S, lane;
-  bool regs;
-  double v[kMaxS];
-  __device__ VelAxis(const double* vel_, int nV_, int lane_) : vel(vel_), nV(nV_), S((nV_ + 63) / 64), lane(lane_) {
-    regs = nV <= 64 * kMaxS;
-#pragma unroll
-    for (int k = 0; k < kMaxS; ++k) {
-      const int r = lane * S + k;
-      v[k] = (regs && k < S && r < nV) ? vel[r] : 0.0;
-    }
-  }
-  // first row whose velocity satisfies the monotone predicate (rows past nV count as satisfying it), nV if none
-  template <class P>
-  __device__ __forceinline__ int first(P pred) const {
-    int f = S;
-#pragma unroll
-    for (int k = 0; k < kMaxS; ++k) {
-      const int r = lane * S + k;
-      if (k < S && f == S && (r >= nV || pred(v[k]))) f = k;
-    }
-    const uint64_t m = __ballot(f < S);
-    if (m == 0) return nV;
-    const int L = __ffsll((unsigned long long)m) - 1;
-    return min(L * S + __shfl(f, L), nV);
-  }
-  __device__ __forceinline__ int below(double x) const {  // first_below
-    return regs ? first([x](double u) { return u < x; }) : first_below(vel, nV, x);
-  }
-  __device__ __forceinline__ int at_or_below(double x) const {  // first_at_or_below
-    return regs ? first([x](double u) { return u <= x; }) : first_at_or_below(vel, nV, x);
-  }
-  __device__ __forceinline__ double at(int r) const {  // vel[r] for a wave-uniform row r
-    if (!regs) return vel[r];
-    const int k = r % S;
-    double u = 0.0;
-#pragma unroll
-    for (int j = 0; j < kMaxS; ++j) u = j == k ? v[j] : u;
-    return __shfl(u, r / S);
-  }
-};
-
 // argmax of column c over rows [r0, r1) (first max wins); -1 when the range is empty
 __device__ __forceinline__ int column_argmax(const float* __restrict__ F, int nF, int c, int r0, int r1, int lane) {
   float best = 0.f;
@@ -191,17 +102,17 @@ __device__ __forceinline__ int column_argmax(const float* __restrict__ F, int nF
   return row;
 }
 
-constexpr int kMaxBand = 1024;
+// The columns of a stored image fv[b] ([nV][nF]) for ridge_walk: band column i is image column c0 + i.
+struct ImageColumns {
+  const float* F;
+  int nF, c0, lane;
+  __device__ __forceinline__ void first(int) {}
+  __device__ __forceinline__ int argmax(int i, int, int r0, int r1) { return column_argmax(F, nF, c0 + i, r0, r1, lane); }
+};
 
 // One wave per (image b, ridge):  extract_ridge_ref_idx (modules/utils.py:621-678) on the band of
-// columns [c0, c0 + nb) of fv[b] ([nV][nF], rows = velocities in descending order vel[r]).
-//   ref == INT32_MIN:  vel_max mode (ref_freq_idx=None), raw picks over rows at/after
-//             argmin |vel_max - vel| (no smoothing)
-//   vref:     per-column reference velocities (ref_vel(freq)), window (vref - sigma, vref + sigma)
-//   else:     pick at column ref over all rows, then walk backward / forward with the window
-//             (v_prev - sigma, v_prev + sigma); -nb <= ref < 0 is a Python index with the reference's
-//             loop order (below); savgol(sgl, 2, mode='interp') of the picks.
-// status[b] = 0, or 1 when a window holds no velocity (np.argmax of an empty slice raises).
+// columns [c0, c0 + nb) of fv[b] ([nV][nF], rows = velocities in descending order vel[r]); the modes and the walk
+// are ridge_walk's (ridge_walk.h).
 __global__ __launch_bounds__(64) void ridge_kernel(const float* __restrict__ fv, int64_t b_stride, int32_t nV,
                                                    int32_t nF, int32_t c0, int32_t nb, const double* __restrict__ vel,
                                                    int32_t ref, double sigma, double vel_max,
@@ -210,96 +121,8 @@ __global__ __launch_bounds__(64) void ridge_kernel(const float* __restrict__ fv,
                                                    double* __restrict__ picks) {
   __shared__ double pick[kMaxBand];
   const int b = blockIdx.x, lane = threadIdx.x;
-  const float* F = fv + (int64_t)b * b_stride;
-  double* o = out + (int64_t)b * nb;
-  int err = 0;
-  if (ref == INT32_MIN) {
-    // max_idx = argmin |vel_max - vel| (first of equal distances)
-    double bd = INFINITY;
-    int bi = nV;
-    for (int r = lane; r < nV; r += 64) {
-      const double d = fabs(vel_max - vel[r]);
-      if (d < bd || (d == bd && r < bi)) {
-        bd = d;
-        bi = r;
-      }
-    }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-      const double d2 = __shfl_xor(bd, s);
-      const int i2 = __shfl_xor(bi, s);
-      if (d2 < bd || (d2 == bd && i2 < bi)) {
-        bd = d2;
-        bi = i2;
-      }
-    }
-    for (int i = 0; i < nb; ++i) {
-      const int r = column_argmax(F, nF, c0 + i, bi, nV, lane);
-      if (lane == 0) {
-        o[i] = r >= 0 ? vel[r] : NAN;
-        if (picks) picks[(int64_t)b * nb + i] = o[i];  // nothing is smoothed here: the raw picks are the result
-      }
-      err |= r < 0;
-    }
-    if (lane == 0) status[b] = err;
-    return;
-  }
-  const VelAxis ax(vel, nV, lane);
-  // the walk over columns i_begin, i_begin + dir, ... (i_end excluded) from the pick velocity v; returns the last pick
-  auto walk = [&](int i_begin, int i_end, int dir, double v) {
-    for (int i = i_begin; i != i_end; i += dir) {
-      const int r0 = ax.below(v + sigma), r1 = ax.at_or_below(v - sigma);
-      const int r = column_argmax(F, nF, c0 + i, r0, r1, lane);
-      err |= r < 0;
-      v = r >= 0 ? ax.at(r) : NAN;  // (r is wave-uniform: every lane takes part in the shuffle)
-      if (lane == 0) pick[i] = v;
-    }
-    return v;
-  };
-  if (vref) {
-    for (int i = 0; i < nb; ++i) {
-      const int r0 = ax.below(vref[i] + sigma), r1 = ax.at_or_below(vref[i] - sigma);
-      const int r = column_argmax(F, nF, c0 + i, r0, r1, lane);
-      err |= r < 0;
-      const double pv = r >= 0 ? ax.at(r) : NAN;
-      if (lane == 0) pick[i] = pv;
-    }
-  } else if (ref < 0) {
-    // a negative reference index is a Python index: out[ref] is column nb + ref, the backward loop
-    // range(ref - 1, -1, -1) is empty, and range(ref + 1, len(freq)) walks columns nb + ref + 1 ..
-    // nb - 1 and then 0 .. nb - 1 again, seeded by out[-1] (modules/utils.py:662-671)
-    const int k0 = nb + ref;
-    const int rr = column_argmax(F, nF, c0 + k0, 0, nV, lane);
-    const double v = rr >= 0 ? ax.at(rr) : NAN;
-    if (lane == 0) pick[k0] = v;
-    walk(0, nb, 1, walk(k0 + 1, nb, 1, v));
-  } else {
-    const int rr = column_argmax(F, nF, c0 + ref, 0, nV, lane);
-    const double vr = rr >= 0 ? ax.at(rr) : NAN;  // wave-uniform (every lane holds the reduced row)
-    if (lane == 0) pick[ref] = vr;
-    walk(ref - 1, -1, -1, vr);  // backward
-    walk(ref + 1, nb, 1, vr);   // forward
-  }
-  __syncthreads();
-  if (picks)  // the raw picks before smoothing (parity checks of each pick)
-    for (int i = lane; i < nb; i += 64) picks[(int64_t)b * nb + i] = pick[i];
-  // savgol_filter(picks, sgl, 2) with mode='interp': interior taps h, edge fits el / er
-  const int half = sgl / 2;
-  const double* h = sg;
-  const double* el = sg + sgl;
-  const double* er = el + half * sgl;
-  for (int i = lane; i < nb; i += 64) {
-    double acc = 0.0;
-    if (i < half) {
-      for (int t = 0; t < sgl; ++t) acc += el[i * sgl + t] * pick[t];
-    } else if (i >= nb - half) {
-      for (int t = 0; t < sgl; ++t) acc += er[(i - (nb - half)) * sgl + t] * pick[nb - sgl + t];
-    } else {
-      for (int t = 0; t < sgl; ++t) acc += h[t] * pick[i - half + t];
-    }
-    o[i] = acc;
-  }
-  if (lane == 0) status[b] = err;
+  ImageColumns src{fv + (int64_t)b * b_stride, nF, c0, lane};
+  ridge_walk(src, b, lane, nV, nb, vel, ref, sigma, vel_max, vref, sg, sgl, out, status, picks, pick);
 }
 
 }  // namespace dvh

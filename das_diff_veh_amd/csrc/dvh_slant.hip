@@ -11,7 +11,9 @@
 // once, and its powers w^r by the recurrence w^r = w^(r-1) w; up to kSlRegRows rows the powers stay in registers and
 // are reused by every gather of the lane's loop (4 FMAs per row and gather), above that the power runs inside the row
 // loop (8 FMAs).  The rows are summed in ascending order by one lane, so an image does not depend on the batch it is
-// part of or on the launch geometry.  Small f-v grids with many gathers split the gathers over gridDim.z.
+// part of or on the launch geometry.  Small f-v grids with many gathers split the gathers over gridDim.z.  The
+// operations of one pair are slant_pair.h's, shared with the ridge walk that evaluates pairs in place
+// (dvh_slant_ridge.hip) and must store the same bits.
 //
 // Measured (tools/bench_slant.py, DESIGN.md "Phase-shift dispersion"): 512 gathers of 19 rows on 512 x 1 000 pairs take
 // 4.6 ms, 14-15 % of the float64 FMA floor (4.2 ms right after the time DFT wrote D).  The FMA pipe does not bound it:
@@ -27,6 +29,7 @@
 
 #include "dvh_common.h"
 #include "dvh.h"
+#include "slant_pair.h"
 
 namespace dvh {
 
@@ -57,8 +60,7 @@ __device__ __forceinline__ bool slant_lane(const SlantArgs& a, int64_t& p, doubl
   if (p >= a.n_pair) return false;
   const int64_t v = p / a.nF;
   const int32_t f = (int32_t)(p - v * a.nF);
-  const double theta = 2.0 * M_PI * a.freqs[f] * a.dx / a.vels[v];
-  sincos(theta, &s, &c);
+  slant_steer(a.freqs[f], a.dx, a.vels[v], c, s);
   Dp = a.D + (int64_t)a.row0 * a.n_fb + a.fb[f];
   return true;
 }
@@ -73,10 +75,7 @@ __global__ __launch_bounds__(kSlThreads) void slant_reg_kernel(const SlantArgs a
   pr[0] = 1.0;
   pi[0] = 0.0;
 #pragma unroll
-  for (int r = 1; r < NR; ++r) {
-    pr[r] = fma(pr[r - 1], c, -(pi[r - 1] * s));
-    pi[r] = fma(pr[r - 1], s, pi[r - 1] * c);
-  }
+  for (int r = 1; r < NR; ++r) slant_next_power(pr[r - 1], pi[r - 1], c, s, pr[r], pi[r]);
   const int64_t g_stride = (int64_t)a.nch * a.n_fb;
   for (int32_t b = blockIdx.z; b < a.B; b += gridDim.z) {
     const double2* Db = Dp + (int64_t)b * g_stride;
@@ -90,14 +89,9 @@ __global__ __launch_bounds__(kSlThreads) void slant_reg_kernel(const SlantArgs a
         if (r0 + u < NR) d[u] = Db[(int64_t)(r0 + u) * a.n_fb];
 #pragma unroll
       for (int u = 0; u < kSlLoad; ++u)
-        if (r0 + u < NR) {
-          ar = fma(d[u].x, pr[r0 + u], ar);
-          ar = fma(-d[u].y, pi[r0 + u], ar);
-          ai = fma(d[u].x, pi[r0 + u], ai);
-          ai = fma(d[u].y, pr[r0 + u], ai);
-        }
+        if (r0 + u < NR) slant_add_row(d[u], pr[r0 + u], pi[r0 + u], ar, ai);
     }
-    a.fv[(int64_t)b * a.b_stride + p] = (float)sqrt(fma(ar, ar, ai * ai));
+    a.fv[(int64_t)b * a.b_stride + p] = slant_magnitude(ar, ai);
   }
 }
 
@@ -112,16 +106,13 @@ __global__ __launch_bounds__(kSlThreads) void slant_run_kernel(const SlantArgs a
     const double2* Db = Dp + (int64_t)b * g_stride;
     double ar = 0.0, ai = 0.0, wr = 1.0, wi = 0.0;
     for (int r = 0; r < a.n_row; ++r) {
-      const double2 d = Db[(int64_t)r * a.n_fb];
-      ar = fma(d.x, wr, ar);
-      ar = fma(-d.y, wi, ar);
-      ai = fma(d.x, wi, ai);
-      ai = fma(d.y, wr, ai);
-      const double nr = fma(wr, c, -(wi * s));
-      wi = fma(wr, s, wi * c);
+      slant_add_row(Db[(int64_t)r * a.n_fb], wr, wi, ar, ai);
+      double nr, ni;
+      slant_next_power(wr, wi, c, s, nr, ni);
       wr = nr;
+      wi = ni;
     }
-    a.fv[(int64_t)b * a.b_stride + p] = (float)sqrt(fma(ar, ar, ai * ai));
+    a.fv[(int64_t)b * a.b_stride + p] = slant_magnitude(ar, ai);
   }
 }
 

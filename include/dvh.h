@@ -259,6 +259,19 @@ int dvh_ridge(const float* fv, int64_t b_stride, int32_t B, int32_t nV, int32_t 
               const double* vel, int32_t ref, double sigma, double vel_max, const double* vref, const double* sg,
               int32_t sgl, double* out, int32_t* status, double* picks, void* stream);
 
+/* dvh_ridge on the phase-shift image of dvh_disp_slant without forming it: the walk computes the values it compares,
+ * float32(| sum_{r < n_row} D[b*n_row + r][fb[c0 + i]] * exp(+i 2 pi freqs[c0 + i] (dx r) / vel[row]) |), by the
+ * arithmetic of dvh_disp_slant, so that every compared value equals, bit for bit, what dvh_disp_slant stores for the
+ * same D (all n_row rows of a gather: nch = n_row, row0 = 0) and velocities vel[nV], strictly descending.  D, n_fb,
+ * fb[nF], freqs[nF] and dx as dvh_disp_slant takes them; the band [c0, c0 + nb), ref, sigma, vel_max, vref, sg, sgl,
+ * out, status and picks as dvh_ridge takes them, with the same results and the same refusals (-2 for a null pointer,
+ * a negative count, n_fb <= 0, a band outside nF or a ref outside the band; -4 for an even sgl, sgl > nb or nb > 1024),
+ * and -4 for n_row > 1024.  B == 0 launches nothing.  The caller validates fb against n_fb on the host. */
+int dvh_slant_ridge(const double* D, int32_t B, int32_t n_row, int32_t n_fb, const int32_t* fb, const double* freqs,
+                    int32_t nF, double dx, int32_t c0, int32_t nb, const double* vel, int32_t nV, int32_t ref,
+                    double sigma, double vel_max, const double* vref, const double* sg, int32_t sgl, double* out,
+                    int32_t* status, double* picks, void* stream);
+
 /* ---------------------------------------------------------------- preprocessing
  * dtype: 0 float32, 1 float64; data modified in place. */
 
