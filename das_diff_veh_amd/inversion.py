@@ -1,0 +1,366 @@
+"""Rayleigh-wave forward model and swarm inversion on the device: the stage of inversion_diff_speed.ipynb and
+inversion_diff_weight.ipynb (disba's ``surf96`` and evodcinv's ``EarthModel.invert``).
+
+Neither disba nor evodcinv is restated.  What is computed here is this build's own definition, documented in DESIGN.md:
+
+  forward    dvh_rayleigh_modes: the secular function of csrc/rayleigh.h (real motion-stress vectors, the analytic
+             layer propagator, re-orthonormalised sublayers), scanned at c_k = fma(k, dc, c_min) below the half-space
+             beta; mode m is the (m + 1)-th sign change, refined to ``tol`` relative.  Roots closer than ``dc`` vanish
+             in pairs, as in surf96's search.  Pinned to an 80-digit Thomson-Haskell oracle (tests/rayleigh_ref.py).
+  misfit     dvh_curve_misfit: sum_i w_i sqrt(mean_j(((obs - c) / sigma)^2)) / sum_i w_i over the curves, +inf for a
+             model that lacks a sampled mode.
+  optimizer  global-best particle swarm on the unit cube of the bounds with the constriction values w = 0.7298,
+             c1 = c2 = 1.49618; positions clamped to the cube, parameters with equal bounds held fixed.  evodcinv's
+             "cpso" adds a competitive restart of particles, which is not restated: ``optimizer="cpso"`` raises.
+
+``rayleigh_modes`` and ``EarthModel.invert`` are device work (float64) with no CPU fallback; all ``maxrun`` runs advance
+together as independent swarms of one batch, one dvh_rayleigh_modes and one dvh_curve_misfit launch per iteration,
+and nothing is read back before the last iteration.
+
+The notebooks' import swap::
+
+    from das_diff_veh_amd.inversion import EarthModel, Layer, Curve, phase_velocity
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import _lib
+from .device import default_device
+
+MAX_LAYERS = 32  # DVH_RAYLEIGH_MAX_LAYERS
+MAX_MODES = 16   # DVH_RAYLEIGH_MAX_MODES
+PSO_W, PSO_C1, PSO_C2 = 0.7298, 1.49618, 1.49618
+
+
+# --------------------------------------------------------------------------------------------------- forward calls
+
+def _modes_into(models, periods, need, c_min, dc, tol, n_mode, out_c, out_count):
+    M, n_layer, _ = models.shape
+    _lib.call("dvh_rayleigh_modes", _lib.ptr(models), M, n_layer, _lib.ptr(periods), periods.numel(), _lib.ptr(need),
+              float(c_min), float(dc), float(tol), int(n_mode), _lib.ptr(out_c), _lib.ptr(out_count),
+              _lib.stream_of(models.device))
+
+
+def rayleigh_modes(models, periods, n_mode, dc=0.005, c_min=None, tol=1e-9, need=None, return_count=False):
+    """Modal Rayleigh phase velocities (km/s) of layered models on the device.
+
+    models   float64 device tensor [M, n_layer, 4] of (h km, vp km/s, vs km/s, rho g/cm^3); the last layer is the
+             half-space
+    periods  float64 device tensor [P] (s)
+    need     None (all ``n_mode`` modes at every period) or int32 [P]: the modes wanted per period, 0 skips it
+    c_min    where the scan starts; None takes 0.8 min(vs) of this call's models (one read-back)
+    ->       [M, P, n_mode], NaN where a mode is not wanted or has no root below the model's half-space vs (and, with
+             ``return_count``, the int32 [M, P] number of roots bracketed)
+    """
+    if not (isinstance(models, torch.Tensor) and models.is_cuda):
+        raise RuntimeError("rayleigh_modes needs device tensors (no CPU fallback)")
+    if models.dim() != 3 or models.shape[-1] != 4 or models.dtype != torch.float64:
+        raise ValueError("models must be float64 [M, n_layer, 4]")
+    if not 1 <= models.shape[1] <= MAX_LAYERS:
+        raise ValueError(f"1 .. {MAX_LAYERS} layers")
+    if not 1 <= int(n_mode) <= MAX_MODES:
+        raise ValueError(f"1 .. {MAX_MODES} modes")
+    dev = models.device
+    models = models.contiguous()
+    periods = torch.as_tensor(periods, dtype=torch.float64, device=dev).reshape(-1).contiguous()
+    M, P = models.shape[0], periods.numel()
+    if need is None:
+        need = torch.full((P,), int(n_mode), dtype=torch.int32, device=dev)
+    else:
+        need = torch.as_tensor(need, device=dev).to(torch.int32).reshape(-1).contiguous()
+        if need.numel() != P:
+            raise ValueError("need must have one entry per period")
+    out_c = torch.empty((M, P, int(n_mode)), dtype=torch.float64, device=dev)
+    out_count = torch.empty((M, P), dtype=torch.int32, device=dev)
+    if M and P:
+        if c_min is None:
+            c_min = 0.8 * float(models[:, :, 2].min())
+        _modes_into(models, periods, need, c_min, dc, tol, n_mode, out_c, out_count)
+    return (out_c, out_count) if return_count else out_c
+
+
+def phase_velocity(period, thickness, velocity_p, velocity_s, density, mode=0, dc=0.005):
+    """The notebooks' ``surf96(period, thickness, velocity_p, velocity_s, density, mode, 0, rayleigh, dc)`` call of
+    plot_predicted_curve: NumPy in, the phase velocity (km/s) of Rayleigh mode ``mode`` at every period out, NaN where
+    the mode does not exist (so the notebooks' ``c > 0`` filter drops it)."""
+    dev = default_device()
+    layers = np.stack([np.asarray(a, np.float64).reshape(-1) for a in (thickness, velocity_p, velocity_s, density)], 1)
+    period = np.ascontiguousarray(np.asarray(period, np.float64).reshape(-1))  # the notebooks pass reversed views
+    if not 0 <= int(mode) < MAX_MODES:
+        raise ValueError(f"mode must be 0 .. {MAX_MODES - 1}")
+    c = rayleigh_modes(torch.from_numpy(np.ascontiguousarray(layers[None])).to(dev), torch.from_numpy(period).to(dev),
+                       int(mode) + 1, dc=dc)
+    return c[0, :, int(mode)].cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------- misfit
+
+@dataclass
+class SampleTable:
+    """The curves of one inversion as dvh_curve_misfit takes them (device tensors) over the union of their periods."""
+    periods: torch.Tensor
+    need: torch.Tensor
+    n_mode: int
+    sample_period: torch.Tensor
+    sample_mode: torch.Tensor
+    sample_obs: torch.Tensor
+    sample_sigma: torch.Tensor
+    sample_curve: torch.Tensor
+    curve_weight: torch.Tensor
+
+
+def sample_table(curves, device=None):
+    """The union of the curves' periods, the modes needed at each (the highest any curve samples there, plus one) and
+    the sample table in curve order."""
+    dev = device or default_device()
+    curves = list(curves)
+    if not curves:
+        raise ValueError("no curves")
+    for c in curves:
+        c.check()
+    periods = np.unique(np.concatenate([c.period for c in curves]))
+    need = np.zeros(periods.size, np.int32)
+    sp, sm, so, ss, sc = [], [], [], [], []
+    for i, c in enumerate(curves):
+        at = np.searchsorted(periods, c.period)
+        np.maximum.at(need, at, c.mode + 1)
+        sp.append(at)
+        sm.append(np.full(at.size, c.mode))
+        so.append(c.data)
+        ss.append(np.ones(at.size) if c.uncertainties is None else c.uncertainties)
+        sc.append(np.full(at.size, i))
+
+    def put(parts, dtype):
+        return torch.from_numpy(np.ascontiguousarray(np.concatenate(parts), dtype=dtype)).to(dev)
+
+    return SampleTable(torch.from_numpy(periods).to(dev), torch.from_numpy(need).to(dev), int(need.max()),
+                       put(sp, np.int32), put(sm, np.int32), put(so, np.float64), put(ss, np.float64),
+                       put(sc, np.int32), put([[c.weight for c in curves]], np.float64))
+
+
+def curve_misfit(c, table, out=None):
+    """dvh_curve_misfit of c [M, P, n_mode] (a rayleigh_modes result on ``table.periods``) -> float64 [M]."""
+    M, P, n_mode = c.shape
+    if P != table.periods.numel() or n_mode != table.n_mode or c.dtype != torch.float64 or not c.is_contiguous():
+        raise ValueError("c must be contiguous float64 [M, len(table.periods), table.n_mode]")
+    if out is None:
+        out = torch.empty(M, dtype=torch.float64, device=c.device)
+    _lib.call("dvh_curve_misfit", _lib.ptr(c), M, P, n_mode, _lib.ptr(table.sample_period),
+              _lib.ptr(table.sample_mode), _lib.ptr(table.sample_obs), _lib.ptr(table.sample_sigma),
+              _lib.ptr(table.sample_curve), table.sample_obs.numel(), _lib.ptr(table.curve_weight),
+              table.curve_weight.numel(), _lib.ptr(out), _lib.stream_of(c.device))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------- the notebooks' classes
+
+class Layer:
+    """Search bounds of one layer: thickness (km), S-wave velocity (km/s) and Poisson's ratio, each (low, high)."""
+
+    def __init__(self, thickness, velocity_s, poisson=(0.2, 0.4)):
+        self.thickness, self.velocity_s, self.poisson = (self._pair(v) for v in (thickness, velocity_s, poisson))
+        if self.thickness[0] < 0.0 or self.velocity_s[0] <= 0.0 or not 0.0 <= self.poisson[0] <= self.poisson[1] < 0.5:
+            raise ValueError("thickness >= 0, velocity_s > 0 and 0 <= poisson < 0.5")
+
+    @staticmethod
+    def _pair(v):
+        lo, hi = (float(x) for x in v)
+        if not lo <= hi:
+            raise ValueError(f"bounds {v!r} are not (low, high)")
+        return lo, hi
+
+    def __repr__(self):
+        return f"Layer(thickness={self.thickness}, velocity_s={self.velocity_s}, poisson={self.poisson})"
+
+
+class Curve:
+    """One observed dispersion curve: periods (s), velocities (km/s), mode number, wave and type, weight and
+    uncertainties (km/s; None weighs every sample alike)."""
+
+    def __init__(self, period, data, mode, wave, type, weight=1.0, uncertainties=None):
+        self.period = np.asarray(period, np.float64).reshape(-1)
+        self.data = np.asarray(data, np.float64).reshape(-1)
+        self.mode, self.wave, self.type, self.weight = int(mode), wave, type, float(weight)
+        self.uncertainties = None if uncertainties is None else np.asarray(uncertainties, np.float64).reshape(-1)
+        self.check()
+
+    def check(self):
+        if self.wave != "rayleigh":
+            raise ValueError(f"wave {self.wave!r}: only 'rayleigh' curves are inverted")
+        if self.type != "phase":
+            raise ValueError(f"type {self.type!r}: only 'phase' velocities are inverted")
+        if not 0 <= self.mode < MAX_MODES:
+            raise ValueError(f"mode must be 0 .. {MAX_MODES - 1}")
+        if self.period.size == 0 or self.data.size != self.period.size:
+            raise ValueError("period and data must have the same, non-zero length")
+        if self.uncertainties is not None and self.uncertainties.size != self.period.size:
+            raise ValueError("uncertainties must match period")
+        if not (np.all(self.period > 0) and np.all(np.isfinite(self.data)) and self.weight > 0):
+            raise ValueError("periods and weight must be positive, data finite")
+        if self.uncertainties is not None and not np.all(self.uncertainties > 0):
+            raise ValueError("uncertainties must be positive")
+
+
+@dataclass
+class InversionResult:
+    """Every model the swarms evaluated, in (run, iteration, particle) order.
+
+    xs       [n_eval, 3 n - 1]  parameters [h(0 .. n-2), vs(0 .. n-1), nu(0 .. n-1)]
+    models   [n_eval, n, 4]     (h, vp, vs, rho) rows; ``model.T`` unpacks into phase_velocity's arguments
+    misfits  [n_eval]
+    model, misfit               the best of them
+    global_misfits [maxrun, maxiter]  each run's best-so-far after every iteration, as the optimizer held it
+    """
+    xs: np.ndarray
+    models: np.ndarray
+    misfits: np.ndarray
+    global_misfits: np.ndarray
+    maxrun: int
+    popsize: int
+    maxiter: int
+    timings: dict = field(default_factory=dict)
+
+    @property
+    def model(self):
+        return self.models[int(np.argmin(self.misfits))]
+
+    @property
+    def misfit(self):
+        return self.misfits.min()
+
+
+class EarthModel:
+    """evodcinv's EarthModel as the notebooks use it: add(Layer) top to bottom, configure(...), invert(curves)."""
+
+    def __init__(self):
+        self.layers = []
+        self._configured = False
+
+    def add(self, layer):
+        if not isinstance(layer, Layer):
+            raise TypeError("add() takes a Layer")
+        if len(self.layers) == MAX_LAYERS:
+            raise ValueError(f"at most {MAX_LAYERS} layers")
+        self.layers.append(layer)
+        return self
+
+    def configure(self, optimizer="pso", misfit="rmse", density=None, optimizer_args=None, dc=0.005):
+        """density: a callable of vp (km/s) made of arithmetic that a torch tensor takes, such as the notebooks'
+        ``lambda vp: 1.56 + 0.186 * vp`` (it is applied to the swarm's device tensor inside the loop).
+        optimizer_args: popsize, maxiter, seed (``workers`` is accepted and ignored)."""
+        if optimizer == "cpso":
+            raise ValueError('optimizer "cpso": its competitive restart is not restated here; pass optimizer="pso"')
+        if optimizer != "pso":
+            raise ValueError(f'optimizer {optimizer!r}: only "pso" is built')
+        if misfit != "rmse":
+            raise ValueError(f'misfit {misfit!r}: only "rmse" is built')
+        if not callable(density):
+            raise ValueError("density must be a callable of vp (evodcinv's named curves are not restated)")
+        args = dict(popsize=10, maxiter=100, seed=None, workers=None)
+        unknown = set(optimizer_args or {}) - set(args)
+        if unknown:
+            raise ValueError(f"unknown optimizer_args {sorted(unknown)}")
+        args.update(optimizer_args or {})
+        if int(args["popsize"]) < 2 or int(args["maxiter"]) < 1 or not float(dc) > 0.0:
+            raise ValueError("popsize >= 2, maxiter >= 1 and dc > 0")
+        self.density, self.dc = density, float(dc)
+        self.popsize, self.maxiter, self.seed = int(args["popsize"]), int(args["maxiter"]), args["seed"]
+        self._configured = True
+        return self
+
+    def bounds(self):
+        """(low, high) of the parameter vector [h(0 .. n-2), vs(0 .. n-1), nu(0 .. n-1)]."""
+        L = self.layers
+        rows = [l.thickness for l in L[:-1]] + [l.velocity_s for l in L] + [l.poisson for l in L]
+        b = np.array(rows, np.float64)
+        return b[:, 0].copy(), b[:, 1].copy()
+
+    def models_of(self, xs):
+        """Parameters [..., 3 n - 1] (a device tensor) -> (h, vp, vs, rho) rows [..., n, 4]; the half-space's h is 0."""
+        n = len(self.layers)
+        h, vs, nu = xs[..., :n - 1], xs[..., n - 1:2 * n - 1], xs[..., 2 * n - 1:]
+        vp = vs * torch.sqrt((2.0 - 2.0 * nu) / (1.0 - 2.0 * nu))
+        rho = torch.as_tensor(self.density(vp), dtype=torch.float64, device=xs.device).expand_as(vp)
+        h = torch.cat([h, torch.zeros_like(vs[..., :1])], dim=-1)
+        return torch.stack([h, vp, vs, rho], dim=-1)
+
+    def invert(self, curves, maxrun=1, profile=False):
+        """``maxrun`` independent swarms of ``popsize`` particles for ``maxiter`` iterations -> InversionResult.
+        ``profile`` records device events around every iteration's dvh_rayleigh_modes launch and the rest of the
+        iteration (read after the last one) into ``result.timings`` (ms per iteration)."""
+        if not self._configured:
+            raise ValueError("configure() the model first")
+        if len(self.layers) < 1:
+            raise ValueError("add() at least one layer")
+        if int(maxrun) < 1:
+            raise ValueError("maxrun >= 1")
+        curves = list(curves)
+        for c in curves:  # before any device work
+            if not isinstance(c, Curve):
+                raise TypeError("invert() takes Curve objects")
+            c.check()
+        dev = default_device()
+        tab = sample_table(curves, dev)
+        R, N, T = int(maxrun), self.popsize, self.maxiter
+        lo_h, hi_h = self.bounds()
+        D = lo_h.size
+        c_min = 0.8 * min(l.velocity_s[0] for l in self.layers)
+        lo = torch.from_numpy(lo_h).to(dev)
+        span = torch.from_numpy(hi_h - lo_h).to(dev)
+        free = (span > 0).to(torch.float64)
+        gen = torch.Generator(device=dev)
+        if self.seed is None:
+            gen.seed()
+        else:
+            gen.manual_seed(int(self.seed))
+
+        def rand():
+            return torch.rand((R, N, D), dtype=torch.float64, device=dev, generator=gen)
+
+        u = rand() * free
+        v = torch.zeros_like(u)
+        pbest_u = u.clone()
+        pbest_f = torch.full((R, N), float("inf"), dtype=torch.float64, device=dev)
+        hist_x = torch.empty((T, R, N, D), dtype=torch.float64, device=dev)
+        hist_f = torch.empty((T, R, N), dtype=torch.float64, device=dev)
+        hist_g = torch.empty((T, R), dtype=torch.float64, device=dev)
+        P = tab.periods.numel()
+        c = torch.empty((R * N, P, tab.n_mode), dtype=torch.float64, device=dev)
+        count = torch.empty((R * N, P), dtype=torch.int32, device=dev)
+        events = []
+        for it in range(T):
+            x = hist_x[it]
+            torch.addcmul(lo, u, span, out=x)
+            models = self.models_of(x).reshape(R * N, len(self.layers), 4).contiguous()
+            if profile:
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                ev[0].record()
+            _modes_into(models, tab.periods, tab.need, c_min, self.dc, 1e-9, tab.n_mode, c, count)
+            if profile:
+                ev[1].record()
+            f = curve_misfit(c, tab, out=hist_f[it].view(-1)).view(R, N)
+            better = f < pbest_f
+            pbest_f = torch.where(better, f, pbest_f)
+            pbest_u = torch.where(better[..., None], u, pbest_u)
+            g_f, g_at = pbest_f.min(dim=1)
+            hist_g[it] = g_f
+            g_u = torch.gather(pbest_u, 1, g_at[:, None, None].expand(R, 1, D))
+            v = (PSO_W * v + PSO_C1 * rand() * (pbest_u - u) + PSO_C2 * rand() * (g_u - u)) * free
+            u = torch.clamp(u + v, 0.0, 1.0)
+            if profile:
+                ev[2].record()
+                events.append(ev)
+        # (T, R, N) -> (R, T, N): a run's evaluations are contiguous, in iteration order
+        xs = hist_x.permute(1, 0, 2, 3).reshape(R * T * N, D)
+        models = self.models_of(xs).cpu().numpy()
+        res = InversionResult(xs.cpu().numpy(), models, hist_f.permute(1, 0, 2).reshape(-1).cpu().numpy(),
+                              hist_g.t().contiguous().cpu().numpy(), R, N, T)
+        if profile:
+            torch.cuda.synchronize(dev)
+            res.timings = dict(modes_ms=np.array([e[0].elapsed_time(e[1]) for e in events]),
+                               rest_ms=np.array([e[1].elapsed_time(e[2]) for e in events]))
+        return res

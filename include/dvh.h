@@ -500,6 +500,58 @@ int dvh_qs_curves(const void* x, int32_t dtype, const int64_t* row_off, int32_t 
 int dvh_class_curve_stats(const double* curves, int64_t curve_stride, const int32_t* slots, int32_t n_pass,
                           int32_t n_t, int32_t n_slot, double* mean, double* std, int32_t* count, void* stream);
 
+/* ---------------------------------------------------------------- Rayleigh forward model (inversion notebooks)
+ * The stage the notebooks give to disba's surf96 and evodcinv.  Neither is restated: the secular function, the scan
+ * that defines a mode and the misfit are this library's own definitions, pinned to an 80-digit
+ * Thomson-Haskell oracle by the tests.
+ *
+ * A model is n_layer rows (h, alpha, beta, rho) of float64 in km, km/s, km/s, g/cm^3, top to bottom; the last row is
+ * the half-space and its h is ignored.  The secular function D(c, omega) is the determinant of the two traction
+ * components at the free surface of the two solutions that decay in the half-space (real arithmetic, a sign that is
+ * continuous in c, |D| <= 1: csrc/rayleigh.h). */
+
+#define DVH_RAYLEIGH_MAX_LAYERS 32
+#define DVH_RAYLEIGH_MAX_MODES 16
+
+/* Modal phase velocities of layers[n_model][n_layer][4] at periods[n_period] (s; omega = 2 pi / period), one wave per
+ * (model, period).  The scan is the definition: the points are c_k = fma(k, dc, c_min), k = 0, 1, .. while c_k is
+ * below the model's half-space beta, and mode m is the (m + 1)-th change of sign of D between consecutive points.  Two
+ * roots closer than dc therefore vanish as a pair, as in surf96's search; a dc below the closest pair of roots finds
+ * them all.  need[n_period] (0 .. n_mode, clipped) is the number of modes wanted at a period; the scan stops once
+ * they are bracketed and 0 skips the period.  Each wanted bracket is narrowed 65-fold a step until its width is at
+ * most tol times its lower end, and the midpoint is stored.
+ *   out_c     [n_model][n_period][n_mode] float64, NaN where a mode is not wanted or has no bracket below beta; every
+ *             slot is written
+ *   out_count [n_model][n_period] int32, the brackets found (at most need)
+ * A period <= 0 or NaN gives NaN and 0.  The layer values are the caller's to check (alpha > beta > 0, rho > 0): the
+ * kernel's loops are bounded on any input (256 sublayers a layer, 65 536 scan points), but its values are then
+ * meaningless.
+ * -2: NULL pointers, negative counts, n_layer or n_mode < 1, c_min, dc or tol not positive and finite.
+ * -4: n_layer > 32, n_mode > 16.  n_model = 0 or n_period = 0 returns 0 without a launch. */
+int dvh_rayleigh_modes(const double* layers, int32_t n_model, int32_t n_layer, const double* periods,
+                       int32_t n_period, const int32_t* need, double c_min, double dc, double tol, int32_t n_mode,
+                       double* out_c, int32_t* out_count, void* stream);
+
+/* The misfit of c[n_model][n_period][n_mode] (the layout above) against n_curve observed curves given as one table of
+ * n_sample samples: sample_period and sample_mode index c, sample_obs and sample_sigma are the observed velocity and
+ * its uncertainty, sample_curve (0 .. n_curve - 1) names the curve a sample belongs to.  Per model
+ *   out = sum_i w_i sqrt(mean_j(((obs_j - c_j) / sigma_j)^2)) / sum_i w_i       j over the samples of curve i
+ * in float64, every sum over the samples in table order and over the curves in order.  +inf where any sampled
+ * (period, mode) is NaN or outside c, or a curve has no sample.
+ * -2: NULL pointers, negative counts, n_period, n_mode, n_sample or n_curve < 1.  n_model = 0 returns 0. */
+int dvh_curve_misfit(const double* c, int32_t n_model, int32_t n_period, int32_t n_mode, const int32_t* sample_period,
+                     const int32_t* sample_mode, const double* sample_obs, const double* sample_sigma,
+                     const int32_t* sample_curve, int32_t n_sample, const double* curve_weight, int32_t n_curve,
+                     double* out, void* stream);
+
+/* D(c_host[i], omega) of one model for i < n_c, the same code on the CPU over host memory (no device is touched);
+ * each point takes its own sublayer counts.  c <= 0 gives NaN.  It pins the arithmetic where there is no GPU and is
+ * no fallback: nothing computes curves with it.
+ * -2: NULL pointers, n_layer < 1, n_c < 0, omega not positive and finite, a layer without h >= 0, alpha > beta > 0
+ * and rho > 0.  -4: n_layer > 32.  n_c = 0 returns 0. */
+int dvh_rayleigh_secular_host(const double* layers_host, int32_t n_layer, const double* c_host, int32_t n_c,
+                              double omega, double* out_host);
+
 #ifdef __cplusplus
 }
 #endif
