@@ -76,6 +76,8 @@ SIGNATURES = {
     "dvh_rayleigh_modes": [_p, _i32, _i32, _p, _i32, _p, _f64, _f64, _f64, _i32, _p, _p, _p],
     "dvh_curve_misfit": [_p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _i32, _p, _p],
     "dvh_rayleigh_secular_host": [_p, _i32, _p, _i32, _f64, _p],
+    "dvh_rayleigh_sens": [_p, _i32, _i32, _p, _i32, _p, _i32, _i32, _f64, _p, _p, _p, _p],
+    "dvh_rayleigh_tangent_host": [_p, _i32, _p, _i32, _f64, _p, _i32, _p, _p],
 }
 _RESTYPES = {"dvh_last_error": C.c_char_p, "dvh_qs_curves_workspace": C.c_int64, "dvh_welch_rows_workspace": C.c_int64, "dvh_vsg_stack_workspace": C.c_int64, "dvh_sosfiltfilt_workspace": C.c_int64,
              "dvh_sosfiltfilt_plan_bytes": C.c_int64, "dvh_sos_pole_radius": C.c_double}

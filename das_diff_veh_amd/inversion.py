@@ -20,9 +20,15 @@ and nothing is read back before the last iteration.
 The notebooks' import swap (INTEGRATION.md, section 2k)::
 
     from das_diff_veh_amd.inversion import EarthModel, Layer, Curve, phase_velocity
+    from das_diff_veh_amd.inversion import PhaseSensitivity, group_velocity
+
+``rayleigh_sensitivity`` and ``rayleigh_group`` (dvh_rayleigh_sens: the derivatives of the secular function taken
+through its own recurrences, csrc/rayleigh_tangent.h) give dc/dp of every layer value and the group velocity at the
+roots of ``rayleigh_modes``; ``PhaseSensitivity`` and ``group_velocity`` are their NumPy fronts for the notebooks.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -364,3 +370,116 @@ class EarthModel:
             res.timings = dict(modes_ms=np.array([e[0].elapsed_time(e[1]) for e in events]),
                                rest_ms=np.array([e[1].elapsed_time(e[2]) for e in events]))
         return res
+
+
+# ------------------------------------------------------------------------------------------------- sensitivities
+
+PARAMETERS = ("thickness", "velocity_p", "velocity_s", "density")  # the columns of a layer row, by disba's names
+
+
+def _parameter_columns(parameters):
+    names = (parameters,) if isinstance(parameters, str) else tuple(parameters)
+    for name in names:
+        if name not in PARAMETERS:
+            raise ValueError(f"parameter {name!r}: one of {PARAMETERS}")
+    if not names or len(set(names)) != len(names):
+        raise ValueError("parameters must be distinct names, at least one")
+    return [PARAMETERS.index(name) for name in names]
+
+
+def _sens(models, periods, n_mode, cols, want_u, dc, c_min, tol, need):
+    """dvh_rayleigh_modes, then dvh_rayleigh_sens on its roots -> (polished c, U or None, dc/dp [..., 4] or None)."""
+    c = rayleigh_modes(models, periods, n_mode, dc=dc, c_min=c_min, tol=tol, need=need)
+    dev = models.device
+    models = models.contiguous()
+    periods = torch.as_tensor(periods, dtype=torch.float64, device=dev).reshape(-1).contiguous()
+    M, n_layer, _ = models.shape
+    out_c = torch.empty_like(c)
+    out_u = torch.empty_like(c) if want_u else None
+    out_p = torch.empty(c.shape + (n_layer, 4), dtype=torch.float64, device=dev) if cols else None
+    if c.numel():
+        _lib.call("dvh_rayleigh_sens", _lib.ptr(models), M, n_layer, _lib.ptr(periods), periods.numel(), _lib.ptr(c),
+                  int(n_mode), sum(1 << q for q in cols), float(tol), _lib.ptr(out_c), _lib.ptr(out_u),
+                  _lib.ptr(out_p), _lib.stream_of(dev))
+    return out_c, out_u, out_p
+
+
+def rayleigh_sensitivity(models, periods, n_mode, parameters=PARAMETERS, dc=0.005, c_min=None, tol=1e-9, need=None,
+                         return_modes=False):
+    """The derivative dc/dp of every modal phase velocity with respect to the layer values, on the device.
+
+    models, periods, n_mode, dc, c_min, tol, need   as rayleigh_modes takes them
+    parameters  names out of ("thickness", "velocity_p", "velocity_s", "density"), the order of the last axis
+    ->          [M, P, n_mode, n_layer, len(parameters)] in km/s per unit of the parameter (km, km/s, g/cm^3), NaN where
+                rayleigh_modes has no root; 0 for a row of zero thickness and for the half-space's thickness (and, with
+                ``return_modes``, the roots [M, P, n_mode] after the kernel's Newton step)
+
+    This is the derivative itself, -D_p / D_c of the secular function at the root (dvh_rayleigh_sens), this build's own
+    definition of a sensitivity kernel: it is not scaled by the layer's thickness or value.
+    """
+    cols = _parameter_columns(parameters)
+    c, _, dcdp = _sens(models, periods, n_mode, cols, False, dc, c_min, tol, need)
+    dcdp = dcdp[..., cols].contiguous()
+    return (dcdp, c) if return_modes else dcdp
+
+
+def rayleigh_group(models, periods, n_mode, dc=0.005, c_min=None, tol=1e-9, need=None, return_modes=False):
+    """Modal Rayleigh group velocities U = c / (1 - (omega / c) dc/domega) (km/s) on the device: [M, P, n_mode], NaN
+    where rayleigh_modes has no root (and, with ``return_modes``, the roots after the kernel's Newton step)."""
+    c, u, _ = _sens(models, periods, n_mode, [], True, dc, c_min, tol, need)
+    return (u, c) if return_modes else u
+
+
+def _layer_rows(thickness, velocity_p, velocity_s, density):
+    rows = [np.asarray(a, np.float64).reshape(-1) for a in (thickness, velocity_p, velocity_s, density)]
+    if len({r.size for r in rows}) != 1 or not 1 <= rows[0].size <= MAX_LAYERS:
+        raise ValueError(f"thickness, velocity_p, velocity_s and density need one length, 1 .. {MAX_LAYERS}")
+    return np.ascontiguousarray(np.stack(rows, 1))
+
+
+def group_velocity(period, thickness, velocity_p, velocity_s, density, mode=0, dc=0.005):
+    """The notebooks' ``surf96(period, thickness, velocity_p, velocity_s, density, mode, 1, rayleigh, dc)`` call
+    (itype = 1) of plot_predicted_curve: NumPy in, the group velocity (km/s) of Rayleigh mode ``mode`` at every period
+    out, NaN where the mode does not exist."""
+    if not 0 <= int(mode) < MAX_MODES:
+        raise ValueError(f"mode must be 0 .. {MAX_MODES - 1}")
+    layers = _layer_rows(thickness, velocity_p, velocity_s, density)
+    period = np.ascontiguousarray(np.asarray(period, np.float64).reshape(-1))  # the notebooks pass reversed views
+    dev = default_device()
+    u = rayleigh_group(torch.from_numpy(layers[None]).to(dev), torch.from_numpy(period).to(dev), int(mode) + 1, dc=dc)
+    return u[0, :, int(mode)].cpu().numpy()
+
+
+SensitivityKernel = namedtuple("SensitivityKernel", "depth kernel period velocity mode wave type parameter")
+
+
+class PhaseSensitivity:
+    """disba's ``PhaseSensitivity(thickness, velocity_p, velocity_s, density)`` as inversion_diff_weight.ipynb uses
+    it: ``ps(t, mode=0, wave="rayleigh", parameter="velocity_s")`` -> SensitivityKernel.
+
+    depth     the top of every layer (km)
+    kernel    [n_layer] dc/dp of that layer's parameter (rayleigh_sensitivity's definition, the derivative itself; the
+              half-space's thickness gives 0), NaN if the mode does not exist at ``t``; a NumPy array of its own, so
+              ``s.kernel[-1:] = 0.0`` works
+    velocity  the phase velocity the kernel was taken at
+    """
+
+    def __init__(self, thickness, velocity_p, velocity_s, density, dc=0.005):
+        self.layers = _layer_rows(thickness, velocity_p, velocity_s, density)
+        self.dc = float(dc)
+
+    def __call__(self, t, mode=0, wave="rayleigh", parameter="velocity_s"):
+        if wave != "rayleigh":
+            raise ValueError(f"wave {wave!r}: only 'rayleigh' is built")
+        if not isinstance(parameter, str):
+            raise ValueError("parameter must be one name")
+        _parameter_columns(parameter)
+        if not 0 <= int(mode) < MAX_MODES:
+            raise ValueError(f"mode must be 0 .. {MAX_MODES - 1}")
+        dev = default_device()
+        k, c = rayleigh_sensitivity(torch.from_numpy(self.layers[None]).to(dev),
+                                    torch.tensor([float(t)], dtype=torch.float64, device=dev), int(mode) + 1,
+                                    parameters=(parameter,), dc=self.dc, return_modes=True)
+        depth = np.concatenate([[0.0], np.cumsum(self.layers[:-1, 0])])
+        return SensitivityKernel(depth, k[0, 0, int(mode), :, 0].cpu().numpy(), float(t), float(c[0, 0, int(mode)]),
+                                 int(mode), wave, "phase", parameter)

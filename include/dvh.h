@@ -552,6 +552,34 @@ int dvh_curve_misfit(const double* c, int32_t n_model, int32_t n_period, int32_t
 int dvh_rayleigh_secular_host(const double* layers_host, int32_t n_layer, const double* c_host, int32_t n_c,
                               double omega, double* out_host);
 
+/* Sensitivity kernels and group velocity at the roots c[n_model][n_period][n_mode] of a dvh_rayleigh_modes call on the
+ * same layers and periods, one wave per (model, period, mode).  At a root of D(c, omega, layers)
+ *   dc/dp = -D_p / D_c  for a layer value p,    dc/domega = -D_omega / D_c,    U = c / (1 - (omega / c) dc/domega),
+ * the derivatives taken through the recurrences of the secular function itself (csrc/rayleigh_tangent.h).  The wave
+ * first takes one Newton step c <- c - D / D_c from the given root and keeps it if it moves c by at most 4 tol c (tol:
+ * the width the roots were refined to); everything else is evaluated at that polished root.
+ *   par_mask  bits 0 .. 3 select the columns h, alpha, beta, rho of out_dcdp
+ *   out_c     [n_model][n_period][n_mode] the polished root
+ *   out_u     [n_model][n_period][n_mode] the group velocity (km/s)
+ *   out_dcdp  [n_model][n_period][n_mode][n_layer][4] dc/dp in km/s per unit of the column; an unselected column is
+ *             NaN; a row with h = 0 (skipped by the secular function) and the half-space's h give 0
+ * Each output may be NULL, not all three; every slot of the others is written.  A NaN (or non-positive) root or
+ * period gives NaN in all of them.  The layer values are the caller's to check, as for dvh_rayleigh_modes.
+ * -2: NULL inputs, no output, negative counts, n_layer or n_mode < 1, tol not positive and finite, par_mask outside
+ * 0 .. 15.  -4: n_layer > 32, n_mode > 16.  n_model = 0 or n_period = 0 returns 0 without a launch. */
+int dvh_rayleigh_sens(const double* layers, int32_t n_model, int32_t n_layer, const double* periods, int32_t n_period,
+                      const double* c, int32_t n_mode, int32_t par_mask, double tol, double* out_c, double* out_u,
+                      double* out_dcdp, void* stream);
+
+/* D(c_host[i], omega) and its derivative along each direction of dirs_host[n_dir], on the CPU over host memory (no
+ * device is touched): out_D [n_c], out_dD [n_c][n_dir].  A direction is 0 (c), 1 (omega) or 2 + 4 l + q (column q of
+ * layer l).  out_D equals dvh_rayleigh_secular_host's value; c <= 0 gives NaN.  It measures the tangent arithmetic
+ * where there is no GPU and is no fallback.
+ * -2: NULL pointers, n_layer or n_dir < 1, n_c < 0, omega not positive and finite, a layer without h >= 0,
+ * alpha > beta > 0 and rho > 0, a direction outside 0 .. 1 + 4 n_layer.  -4: n_layer > 32.  n_c = 0 returns 0. */
+int dvh_rayleigh_tangent_host(const double* layers_host, int32_t n_layer, const double* c_host, int32_t n_c,
+                              double omega, const int32_t* dirs_host, int32_t n_dir, double* out_D, double* out_dD);
+
 #ifdef __cplusplus
 }
 #endif
