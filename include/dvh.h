@@ -519,7 +519,9 @@ int dvh_class_curve_stats(const double* curves, int64_t curve_stride, const int3
  * roots closer than dc therefore vanish as a pair, as in surf96's search; a dc below the closest pair of roots finds
  * them all.  need[n_period] (0 .. n_mode, clipped) is the number of modes wanted at a period; the scan stops once
  * they are bracketed and 0 skips the period.  Each wanted bracket is narrowed 65-fold a step until its width is at
- * most tol times its lower end, and the midpoint is stored.
+ * most tol times its lower end, and the midpoint is stored.  A step takes the 64 points that cut the bracket into 65
+ * equal parts, and the first change of sign among them closes the new bracket: of a bracket that holds three roots or
+ * more, the lowest one those points separate is returned.
  *   out_c     [n_model][n_period][n_mode] float64, NaN where a mode is not wanted or has no bracket below beta; every
  *             slot is written
  *   out_count [n_model][n_period] int32, the brackets found (at most need)

@@ -73,9 +73,9 @@ def _system(k, w, al, be, rho):
                       [0, -w * w * rho, -k, 0]])
 
 
-def secular(layers, c, omega):
-    """The secular function at 80 digits (an mpf); layers float64 [n][4], c a float or mpf."""
-    with mp.workdps(DIGITS):
+def secular(layers, c, omega, digits=DIGITS):
+    """The secular function at `digits` digits (an mpf); layers float64 [n][4], c a float or mpf."""
+    with mp.workdps(digits):
         c, w = mp.mpf(c), mp.mpf(omega)
         k = w / c
         L = [[mp.mpf(float(x)) for x in row] for row in layers]
@@ -89,24 +89,25 @@ def secular(layers, c, omega):
         return Y[2, 0] * Y[3, 1] - Y[3, 0] * Y[2, 1]
 
 
-def bisect(layers, omega, lo, hi, width=mp.mpf("1e-25")):
+def bisect(layers, omega, lo, hi, width=mp.mpf("1e-25"), digits=DIGITS):
     """The root in (lo, hi), which must bracket a sign change, to `width`."""
-    with mp.workdps(DIGITS):
+    with mp.workdps(digits):
         lo, hi = mp.mpf(lo), mp.mpf(hi)
-        slo = mp.sign(secular(layers, lo, omega))
-        assert slo * mp.sign(secular(layers, hi, omega)) < 0
+        slo = mp.sign(secular(layers, lo, omega, digits))
+        assert slo * mp.sign(secular(layers, hi, omega, digits)) < 0
         while hi - lo > width:
             mid = (lo + hi) / 2
-            if mp.sign(secular(layers, mid, omega)) == slo:
+            if mp.sign(secular(layers, mid, omega, digits)) == slo:
                 lo = mid
             else:
                 hi = mid
         return (lo + hi) / 2
 
 
-def scan_signs(layers, omega, c_min, dc=DC):
+def scan_signs(layers, omega, c_min, dc=DC, digits=DIGITS):
     """The oracle's sign (+1 / -1) at every scan point."""
-    return np.array([int(mp.sign(secular(layers, float(c), omega))) for c in scan_points(layers, c_min, dc)], np.int8)
+    return np.array([int(mp.sign(secular(layers, float(c), omega, digits))) for c in scan_points(layers, c_min, dc)],
+                    np.int8)
 
 
 def roots_of(layers, omega, c_min, dc=DC, signs=None, which=None):
