@@ -1,0 +1,110 @@
+// The arithmetic of the damped Gauss-Newton step ("Gauss-Newton refinement"), written once for the device
+// kernels and the host entries of dvh_refine.hip.  Every output entry is one sequential chain of operations in an order
+// fixed by the sample table and the shapes: the device gives an entry to one thread, the host to one loop, and the two
+// differ only by the FMA contraction of the device compile.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define DVH_HD __host__ __device__ inline
+#else
+#define DVH_HD inline
+#endif
+
+namespace dvh {
+namespace refine {
+
+constexpr int kMaxParams = 96;  // DVH_LM_MAX_PARAMS
+constexpr int kMaxCurves = 64;  // DVH_LM_MAX_CURVES
+
+// The sample table of dvh_curve_misfit, and the shape of c it indexes.
+struct Table {
+  const int32_t* period;
+  const int32_t* mode;
+  const double* obs;
+  const double* sigma;
+  const int32_t* curve;
+  int n_sample, n_curve, n_period, n_mode;
+};
+
+DVH_HD bool is_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }  // false for NaN
+
+// The (period, mode) slot of sample s in c, or -1 if the sample indexes outside c or names no curve.
+DVH_HD int64_t slot_of(const Table& t, int s) {
+  const int p = t.period[s], m = t.mode[s], i = t.curve[s];
+  if (p < 0 || p >= t.n_period || m < 0 || m >= t.n_mode || i < 0 || i >= t.n_curve) return -1;
+  return (int64_t)p * t.n_mode + m;
+}
+
+DVH_HD double residual(const Table& t, const double* cm, int s) {
+  return (cm[slot_of(t, s)] - t.obs[s]) / t.sigma[s];
+}
+
+DVH_HD double rms_of(double sum_of_squares, int n) { return sqrt(sum_of_squares / (double)n); }
+
+// rho_i and n_i of curve i: the mean over its samples in table order.  All samples must have a slot.
+DVH_HD void curve_rms(const Table& t, const double* cm, int i, double& rho, int& n) {
+  double acc = 0.0;
+  n = 0;
+  for (int s = 0; s < t.n_sample; ++s) {
+    if (t.curve[s] != i) continue;
+    const double r = residual(t, cm, s);
+    acc += r * r;
+    ++n;
+  }
+  rho = rms_of(acc, n);
+}
+
+// f = sum_i w_i rho_i / W and W, over the curves in order.
+DVH_HD double misfit_of(const double* w, const double* rho, int n_curve, double& W) {
+  double num = 0.0;
+  W = 0.0;
+  for (int i = 0; i < n_curve; ++i) {
+    num += w[i] * rho[i];
+    W += w[i];
+  }
+  return num / W;
+}
+
+DVH_HD double curve_factor(double w, double W, int n, double rho, double rho_floor) {
+  return w / (W * (double)n * fmax(rho, rho_floor));
+}
+
+// j_s[k]: row is dcdp's [4 n_layer] values at the sample's slot, chain is [4 n_layer][D].
+DVH_HD double jacobian_entry(const double* row, const double* chain, int n_value, int D, int k, double sigma) {
+  double acc = 0.0;
+  for (int r = 0; r < n_value; ++r) acc += row[r] * chain[(int64_t)r * D + k];
+  return acc / sigma;
+}
+
+// One sample's term of g_k (w = a r) and of H_kl (w = a).
+DVH_HD double add_g(double acc, double w, double jk) { return acc + w * jk; }
+DVH_HD double add_h(double acc, double w, double jk, double jl) { return acc + (w * jk) * jl; }
+
+// Pair p of the lower triangle in row order: p = k (k + 1) / 2 + l, l <= k.
+DVH_HD void pair_of(int p, int& k, int& l) {
+  k = (int)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
+  while (k * (k + 1) / 2 > p) --k;
+  while ((k + 1) * (k + 2) / 2 <= p) ++k;
+  l = p - k * (k + 1) / 2;
+}
+DVH_HD int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // j <= i
+
+// d_k = max(H_kk, 1e-12 max_j H_jj) over the free parameters; the damped diagonal is H_kk + lambda d_k.
+DVH_HD double damped_diagonal(double hkk, double hmax, double lambda) {
+  return hkk + lambda * fmax(hkk, 1e-12 * hmax);
+}
+
+// The steps of the Cholesky solve on the packed lower triangle L (row order) and the right-hand side y.  Entry (i, j)
+// takes its products in the order k = 0 .. j - 1; the solves subtract column by column, which is that same order for
+// every entry of y.
+DVH_HD double chol_reduce(const double* L, int i, int j) {
+  double v = L[tri(i, j)];
+  for (int k = 0; k < j; ++k) v -= L[tri(i, k)] * L[tri(j, k)];
+  return v;
+}
+DVH_HD bool pivot_ok(double v) { return v > 0.0 && is_finite(v); }
+
+}  // namespace refine
+}  // namespace dvh

@@ -25,6 +25,10 @@ The notebooks' import swap (INTEGRATION.md, section 2k)::
 ``rayleigh_sensitivity`` and ``rayleigh_group`` (dvh_rayleigh_sens: the derivatives of the secular function taken
 through its own recurrences, csrc/rayleigh_tangent.h) give dc/dp of every layer value and the group velocity at the
 roots of ``rayleigh_modes``; ``PhaseSensitivity`` and ``group_velocity`` are their NumPy fronts for the notebooks.
+
+``EarthModel.refine`` (dvh_lm_normal, dvh_lm_solve: csrc/refine.h) is a damped Gauss-Newton descent of the misfit from
+the swarm's models, ``InversionResult.run_best()`` or any rows of ``xs``; its objective, step and acceptance rule are
+this build's own ("Gauss-Newton refinement").
 """
 from __future__ import annotations
 
@@ -238,6 +242,96 @@ class InversionResult:
     def misfit(self):
         return self.misfits.min()
 
+    def run_best(self):
+        """[maxrun, 3 n - 1]: the best model each run evaluated (its first, where several tie), the rows that
+        ``EarthModel.refine`` starts from."""
+        per_run = self.misfits.reshape(self.maxrun, -1)
+        at = np.argmin(per_run, axis=1) + np.arange(self.maxrun) * per_run.shape[1]
+        return self.xs[at].copy()
+
+
+def starts_in_bounds(xs, lo, hi):
+    """Whether every row of xs (NumPy or a tensor, [M, D]) lies within one ulp of the cube lo .. hi (NumPy [D]): the
+    test ``EarthModel.refine`` applies to its starts.  lo + u (hi - lo), as ``invert`` forms its models, can round to
+    one ulp above hi at u = 1."""
+    below, above = np.nextafter(lo, -np.inf), np.nextafter(hi, np.inf)
+    if isinstance(xs, torch.Tensor):
+        below, above = (torch.from_numpy(b).to(xs.device) for b in (below, above))
+    return bool(((xs >= below) & (xs <= above)).all())
+
+
+LM_MAX_PARAMS = 96  # DVH_LM_MAX_PARAMS
+LM_MAX_CURVES = 64  # DVH_LM_MAX_CURVES
+LM_RHO_FLOOR = 1e-12
+LM_LAMBDA_MIN, LM_LAMBDA_MAX = 1e-12, 1e12
+
+
+@dataclass
+class RefineResult:
+    """What ``EarthModel.refine`` returns for its M starts (NumPy arrays).
+
+    xs, models        [M, 3 n - 1], [M, n, 4]  the refined models, inside the bounds; a start that was never improved
+                      is returned as given (clamped, if it was an ulp outside)
+    misfits           [M]  dvh_lm_normal's f at ``models`` (polished roots)
+    start_misfits     [M]  the same at the starts
+    history           [maxiter + 1, M]  the kept f after every iteration; row 0 is ``start_misfits``
+    accepted          [maxiter, M] bool  whether the iteration's trial was taken
+    lam               [M]  the damping after the last iteration
+    status            [M] int32  bit 0: the start has f = +inf (a sampled mode is missing) and stayed where it was;
+                      bit 1: the last damped system had no positive pivot (no step was taken from it)
+    gradient, hessian [M, D], [M, D, D]  g and H of the final point, in the unit cube u of the bounds
+    """
+    xs: np.ndarray
+    models: np.ndarray
+    misfits: np.ndarray
+    start_misfits: np.ndarray
+    history: np.ndarray
+    accepted: np.ndarray
+    lam: np.ndarray
+    status: np.ndarray
+    gradient: np.ndarray
+    hessian: np.ndarray
+    timings: dict = field(default_factory=dict)
+
+
+def lm_normal(c, dcdp, chain, table, rho_floor=LM_RHO_FLOOR):
+    """dvh_lm_normal of c [M, P, n_mode] and dcdp [M, P, n_mode, n_layer, 4] (dvh_rayleigh_sens on ``table.periods``)
+    and chain [M, 4 n_layer, D] -> (f [M], g [M, D], H [M, D, D], status int32 [M]) on the device."""
+    M, P, n_mode = c.shape
+    n_layer, D = dcdp.shape[3], chain.shape[2]
+    if P != table.periods.numel() or n_mode != table.n_mode or dcdp.shape != (M, P, n_mode, n_layer, 4) or \
+            chain.shape != (M, 4 * n_layer, D):
+        raise ValueError("c [M, P, n_mode], dcdp [M, P, n_mode, n_layer, 4] and chain [M, 4 n_layer, D] on the table")
+    for t in (c, dcdp, chain):
+        if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("c, dcdp and chain must be contiguous float64 device tensors")
+    dev = c.device
+    f = torch.empty(M, dtype=torch.float64, device=dev)
+    g = torch.empty((M, D), dtype=torch.float64, device=dev)
+    H = torch.empty((M, D, D), dtype=torch.float64, device=dev)
+    status = torch.empty(M, dtype=torch.int32, device=dev)
+    _lib.call("dvh_lm_normal", _lib.ptr(c), _lib.ptr(dcdp), _lib.ptr(chain), M, P, n_mode, n_layer, D,
+              _lib.ptr(table.sample_period), _lib.ptr(table.sample_mode), _lib.ptr(table.sample_obs),
+              _lib.ptr(table.sample_sigma), _lib.ptr(table.sample_curve), table.sample_obs.numel(),
+              _lib.ptr(table.curve_weight), table.curve_weight.numel(), float(rho_floor), _lib.ptr(f), _lib.ptr(g),
+              _lib.ptr(H), _lib.ptr(status), _lib.stream_of(dev))
+    return f, g, H, status
+
+
+def lm_solve(H, g, lam, free):
+    """dvh_lm_solve: (H + lam diag(d)) delta = -g over the parameters with free != 0 -> (delta [M, D], status [M])."""
+    M, D = g.shape
+    if H.shape != (M, D, D) or lam.shape != (M,) or free.shape != (D,) or free.dtype != torch.int32:
+        raise ValueError("H [M, D, D], g [M, D], lam [M] and int32 free [D]")
+    for t in (H, g, lam, free):
+        if not t.is_contiguous() or not t.is_cuda or (t is not free and t.dtype != torch.float64):
+            raise ValueError("H, g and lam must be contiguous float64 device tensors")
+    delta = torch.empty_like(g)
+    status = torch.empty(M, dtype=torch.int32, device=g.device)
+    _lib.call("dvh_lm_solve", _lib.ptr(H), _lib.ptr(g), _lib.ptr(lam), _lib.ptr(free), M, D, _lib.ptr(delta),
+              _lib.ptr(status), _lib.stream_of(g.device))
+    return delta, status
+
 
 class EarthModel:
     """evodcinv's EarthModel as the notebooks use it: add(Layer) top to bottom, configure(...), invert(curves)."""
@@ -369,6 +463,168 @@ class EarthModel:
             torch.cuda.synchronize(dev)
             res.timings = dict(modes_ms=np.array([e[0].elapsed_time(e[1]) for e in events]),
                                rest_ms=np.array([e[1].elapsed_time(e[2]) for e in events]))
+        return res
+
+    def chain(self, xs, span=None):
+        """The derivative of ``models_of``'s rows with respect to the unit cube u of the bounds (x = lo + u (hi - lo)):
+        parameters [M, 3 n - 1] (a device or CPU tensor) -> [M, 4 n, D], row 4 l + q for column q of layer l.
+
+        With g = sqrt((2 - 2 nu) / (1 - 2 nu)): dh/dh = dvs/dvs = 1, dvp/dvs = g, dvp/dnu = vs / (g (1 - 2 nu)^2) and
+        drho = rho'(vp) dvp, each times the parameter's span; rho' is taken by autograd on the density callable (0 for
+        one that returns a constant).  A fixed parameter's column and the half-space's h row are 0.  Torch ops only.
+        ``span`` is hi - lo of ``bounds()`` as a tensor on xs's device, for a caller that holds it already."""
+        n = len(self.layers)
+        D = 3 * n - 1
+        if not isinstance(xs, torch.Tensor) or xs.dim() != 2 or xs.shape[1] != D or xs.dtype != torch.float64:
+            raise ValueError(f"xs must be a float64 tensor [M, {D}]")
+        if span is None:
+            lo_h, hi_h = self.bounds()
+            span = torch.from_numpy(hi_h - lo_h).to(xs.device)
+        xs = xs.detach()
+        vs, nu = xs[:, n - 1:2 * n - 1], xs[:, 2 * n - 1:]
+        g = torch.sqrt((2.0 - 2.0 * nu) / (1.0 - 2.0 * nu))
+        with torch.enable_grad():
+            vp = (vs * g).clone().requires_grad_(True)
+            rho = self.density(vp)
+            if isinstance(rho, torch.Tensor) and rho.requires_grad:
+                drho, = torch.autograd.grad(rho.expand_as(vp).sum(), vp)
+            else:
+                drho = torch.zeros_like(vp)
+        dvp_dvs = g * span[n - 1:2 * n - 1]
+        dvp_dnu = vs / (g * (1.0 - 2.0 * nu) ** 2) * span[2 * n - 1:]
+        out = torch.zeros((xs.shape[0], n, 4, D), dtype=torch.float64, device=xs.device)
+        at = torch.arange(n, device=xs.device)
+        out[:, at[:-1], 0, at[:-1]] = span[:n - 1]
+        out[:, at, 1, n - 1 + at] = dvp_dvs
+        out[:, at, 1, 2 * n - 1 + at] = dvp_dnu
+        out[:, at, 2, n - 1 + at] = span[n - 1:2 * n - 1]
+        out[:, at, 3, n - 1 + at] = drho * dvp_dvs
+        out[:, at, 3, 2 * n - 1 + at] = drho * dvp_dnu
+        return out.reshape(xs.shape[0], 4 * n, D)
+
+    def refine(self, curves, xs, maxiter=20, lam0=1e-3, tol=1e-9, profile=False):
+        """A damped Gauss-Newton (Levenberg-Marquardt) descent of the misfit from each row of ``xs`` -> RefineResult.
+
+        xs       [M, 3 n - 1] inside the bounds, NumPy or a device tensor (rows of ``InversionResult.xs``, or
+                 ``InversionResult.run_best()``).  ``invert`` forms lo + u (hi - lo), which at u = 1 can round to one
+                 ulp above hi: a value within one ulp of the cube is taken and clamped into it.  The models returned
+                 lie inside the bounds exactly
+        maxiter  iterations; every model of the batch advances in lockstep (0 evaluates the starts only)
+        lam0     the damping every model starts with
+        tol      the relative width the roots are refined to, as in ``invert``
+
+        DESIGN.md ("Gauss-Newton refinement") has the definitions.  Per iteration: dvh_lm_solve on the kept g and H,
+        then at the trial points clamp(u + delta, 0, 1) the scan of ``invert`` (dvh_rayleigh_modes with its c_min, dc
+        and need), dvh_rayleigh_sens, dvh_lm_normal and a torch.where selection: the trial is taken iff its f is
+        lower (+inf never is), lambda is divided by 10 on acceptance and multiplied by 10 otherwise, within
+        1e-12 .. 1e12.  Nothing is read back before the end.
+
+        The residuals use the roots after dvh_rayleigh_sens's Newton step, so ``start_misfits`` may differ from
+        ``invert``'s misfit of the same model by the root refinement width over sigma (tol c / sigma per sample).
+        ``profile`` records device events around the launches into ``result.timings`` (ms per iteration)."""
+        if not self._configured:
+            raise ValueError("configure() the model first")
+        n = len(self.layers)
+        if n < 1:
+            raise ValueError("add() at least one layer")
+        D = 3 * n - 1
+        if D > LM_MAX_PARAMS:
+            raise ValueError(f"at most {LM_MAX_PARAMS} parameters")
+        if int(maxiter) < 0 or not (float(lam0) > 0.0 and np.isfinite(lam0)) or \
+                not (float(tol) > 0.0 and np.isfinite(tol)):
+            raise ValueError("maxiter >= 0, lam0 and tol positive and finite")
+        curves = list(curves)
+        for c in curves:  # before any device work
+            if not isinstance(c, Curve):
+                raise TypeError("refine() takes Curve objects")
+            c.check()
+        if not 1 <= len(curves) <= LM_MAX_CURVES:
+            raise ValueError(f"1 .. {LM_MAX_CURVES} curves")
+        lo_h, hi_h = self.bounds()
+        given_tensor = isinstance(xs, torch.Tensor)
+        if given_tensor:
+            if xs.dim() != 2 or xs.shape[1] != D or xs.dtype != torch.float64:
+                raise ValueError(f"xs must be float64 [M, {D}]")
+        else:
+            xs = np.ascontiguousarray(xs, np.float64)
+            if xs.ndim != 2 or xs.shape[1] != D:
+                raise ValueError(f"xs must be [M, {D}]")
+            xs = torch.from_numpy(xs)
+        if not starts_in_bounds(xs, lo_h, hi_h):
+            raise ValueError("xs must lie inside the bounds")
+        dev = default_device()
+        lo, hi = torch.from_numpy(lo_h).to(dev), torch.from_numpy(hi_h).to(dev)
+        x = torch.minimum(torch.maximum(xs.to(dev), lo), hi).contiguous()
+        tab = sample_table(curves, dev)
+        M, T = x.shape[0], int(maxiter)
+        span = hi - lo
+        free = (span > 0).to(torch.int32)
+        c_min = 0.8 * min(l.velocity_s[0] for l in self.layers)
+        P = tab.periods.numel()
+        c0 = torch.empty((M, P, tab.n_mode), dtype=torch.float64, device=dev)
+        count = torch.empty((M, P), dtype=torch.int32, device=dev)
+        c1 = torch.empty_like(c0)
+        dcdp = torch.empty((M, P, tab.n_mode, n, 4), dtype=torch.float64, device=dev)
+        marks = []
+
+        def mark(ev):
+            if profile:
+                ev.append(torch.cuda.Event(enable_timing=True))
+                ev[-1].record()
+
+        def normal_at(x, ev):
+            models = self.models_of(x).contiguous()
+            chain = self.chain(x, span)
+            mark(ev)
+            if M:
+                _modes_into(models, tab.periods, tab.need, c_min, self.dc, tol, tab.n_mode, c0, count)
+            mark(ev)
+            if M:
+                _lib.call("dvh_rayleigh_sens", _lib.ptr(models), M, n, _lib.ptr(tab.periods), P, _lib.ptr(c0),
+                          tab.n_mode, 15, float(tol), _lib.ptr(c1), None, _lib.ptr(dcdp), _lib.stream_of(dev))
+            mark(ev)
+            out = lm_normal(c1, dcdp, chain, tab)
+            mark(ev)
+            return out
+
+        u = torch.where(span > 0, (x - lo) / torch.where(span > 0, span, torch.ones_like(span)), torch.zeros_like(x))
+        u = torch.clamp(u, 0.0, 1.0)
+        f, g, H, start_status = normal_at(x, [])
+        alive = start_status == 0
+        lam = torch.full((M,), float(lam0), dtype=torch.float64, device=dev)
+        history = torch.empty((T + 1, M), dtype=torch.float64, device=dev)
+        accepted = torch.empty((T, M), dtype=torch.bool, device=dev)
+        history[0] = f
+        solve_status = torch.zeros(M, dtype=torch.int32, device=dev)
+        ten = torch.tensor(10.0, dtype=torch.float64, device=dev)  # a tensor: lam / 10.0 would multiply by 0.1
+        for it in range(T):
+            ev = []
+            mark(ev)
+            delta, solve_status = lm_solve(H, g, lam, free)
+            u_t = torch.clamp(u + delta, 0.0, 1.0)
+            x_t = torch.minimum(torch.addcmul(lo, u_t, span), hi)  # lo + (hi - lo) can round to an ulp above hi
+            f_t, g_t, H_t, _ = normal_at(x_t, ev)
+            take = (f_t < f) & alive
+            f = torch.where(take, f_t, f)
+            g = torch.where(take[:, None], g_t, g)
+            H = torch.where(take[:, None, None], H_t, H)
+            u = torch.where(take[:, None], u_t, u)
+            x = torch.where(take[:, None], x_t, x)
+            lam = torch.where(take, torch.clamp(lam / ten, min=LM_LAMBDA_MIN),
+                              torch.clamp(lam * ten, max=LM_LAMBDA_MAX))
+            history[it + 1] = f
+            accepted[it] = take
+            mark(ev)
+            marks.append(ev)
+        status = (start_status & 1) | (solve_status & 2)
+        host = lambda t: t.cpu().numpy()
+        res = RefineResult(host(x), host(self.models_of(x)), host(f), host(history[0]), host(history), host(accepted),
+                           host(lam), host(status), host(g), host(H))
+        if profile:
+            torch.cuda.synchronize(dev)
+            names = ("solve_ms", "modes_ms", "sens_ms", "normal_ms", "select_ms")
+            res.timings = {name: np.array([e[k].elapsed_time(e[k + 1]) for e in marks])
+                           for k, name in enumerate(names)}
         return res
 
 

@@ -582,6 +582,63 @@ int dvh_rayleigh_sens(const double* layers, int32_t n_model, int32_t n_layer, co
 int dvh_rayleigh_tangent_host(const double* layers_host, int32_t n_layer, const double* c_host, int32_t n_c,
                               double omega, const int32_t* dirs_host, int32_t n_dir, double* out_D, double* out_dD);
 
+/* ---------------------------------------------------------------- Gauss-Newton refinement of inverted models
+ * A damped Gauss-Newton (Levenberg-Marquardt) step on dvh_curve_misfit's quantity in the unit cube u of the bounds
+ * (x = lo + u (hi - lo)); the definitions are this library's own ("Gauss-Newton refinement"). */
+
+#define DVH_LM_MAX_PARAMS 96
+#define DVH_LM_MAX_CURVES 64
+
+/* The misfit, its gradient and the Gauss-Newton matrix of n_model models, one workgroup per model.
+ *   c      [n_model][n_period][n_mode]              roots (dvh_rayleigh_sens's out_c)
+ *   dcdp   [n_model][n_period][n_mode][n_layer][4]  its out_dcdp with all four columns
+ *   chain  [n_model][4 n_layer][n_param]            float64, the derivative of the layer values (row 4 l + q: column q
+ *                                                   of layer l) with respect to u
+ * and the sample table, curve weights and counts as dvh_curve_misfit takes them.  With r_s = (c_s - obs_s) / sigma_s,
+ * per curve i of n_i samples rho_i = sqrt(mean_s r_s^2), W = sum_i w_i and a_i = w_i / (W n_i max(rho_i, rho_floor)),
+ * and j_s[k] = (sum_r dcdp[slot of s][r] chain[r][k]) / sigma_s,
+ *   out_f      [n_model]                   sum_i w_i rho_i / W, dvh_curve_misfit's quantity
+ *   out_g      [n_model][n_param]          sum_s a_i(s) r_s j_s, the gradient of f in u
+ *   out_H      [n_model][n_param][n_param] sum_s a_i(s) j_s j_s^T, full and symmetric
+ *   out_status [n_model] int32             0, or 1 for a flagged model
+ * Only the sampled (period, mode) slots of c and dcdp are read; the others may hold anything.  A model is flagged when
+ * a sampled root or any value of a sampled dcdp row is not finite, a sample indexes outside c or names a curve outside
+ * 0 .. n_curve - 1, or a curve has no sample: its f is +inf and its g and H are zeros.  Every entry is one sum over the
+ * samples in table order (r over the layer values in order inside it) and no atomics are used, so a model's outputs
+ * depend neither on n_model nor on its place in the batch.
+ * -2: NULL pointers, negative counts, n_period, n_mode, n_layer, n_param, n_sample or n_curve < 1, rho_floor not
+ * positive and finite.  -4: n_param > 96, n_layer > 32, n_mode > 16, n_curve > 64.  n_model = 0 returns 0 without a
+ * launch. */
+int dvh_lm_normal(const double* c, const double* dcdp, const double* chain, int32_t n_model, int32_t n_period,
+                  int32_t n_mode, int32_t n_layer, int32_t n_param, const int32_t* sample_period,
+                  const int32_t* sample_mode, const double* sample_obs, const double* sample_sigma,
+                  const int32_t* sample_curve, int32_t n_sample, const double* curve_weight, int32_t n_curve,
+                  double rho_floor, double* out_f, double* out_g, double* out_H, int32_t* out_status, void* stream);
+
+/* The damped step of every model, one wave per model: over the parameters k with free_mask[k] != 0,
+ *   A = H + lambda diag(d),  d_k = max(H_kk, 1e-12 max_j H_jj),   A delta = -g
+ * by a float64 Cholesky factorisation of the packed lower triangle in LDS and two triangular solves; only the lower
+ * triangle of H [n_model][n_param][n_param] is read.  g is [n_model][n_param], lambda [n_model], free_mask int32
+ * [n_param] (shared by the models).
+ *   out_delta  [n_model][n_param]  the step; exactly 0 for a parameter that is not free
+ *   out_status [n_model] int32     0, or 2: a pivot that is not positive and finite (so also a model whose H_kk are all
+ *                                  0, or one without a free parameter) or a step that is not finite; delta is then 0
+ *                                  in every parameter, for that model only
+ * -2: NULL pointers, n_model < 0, n_param < 1.  -4: n_param > 96.  n_model = 0 returns 0 without a launch. */
+int dvh_lm_solve(const double* H, const double* g, const double* lambda, const int32_t* free_mask, int32_t n_model,
+                 int32_t n_param, double* out_delta, int32_t* out_status, void* stream);
+
+/* dvh_lm_normal and dvh_lm_solve on the CPU over host memory, from the same header (csrc/refine.h) and in the same
+ * order of operations; no device is touched.  They pin the arithmetic where there is no GPU and are no fallback:
+ * nothing refines models with them.  Arguments, outputs and return codes as above. */
+int dvh_lm_normal_host(const double* c, const double* dcdp, const double* chain, int32_t n_model, int32_t n_period,
+                       int32_t n_mode, int32_t n_layer, int32_t n_param, const int32_t* sample_period,
+                       const int32_t* sample_mode, const double* sample_obs, const double* sample_sigma,
+                       const int32_t* sample_curve, int32_t n_sample, const double* curve_weight, int32_t n_curve,
+                       double rho_floor, double* out_f, double* out_g, double* out_H, int32_t* out_status);
+int dvh_lm_solve_host(const double* H, const double* g, const double* lambda, const int32_t* free_mask,
+                      int32_t n_model, int32_t n_param, double* out_delta, int32_t* out_status);
+
 #ifdef __cplusplus
 }
 #endif
