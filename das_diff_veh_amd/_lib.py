@@ -84,6 +84,10 @@ SIGNATURES = {
     "dvh_lm_normal_host": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _i32, _f64, _p, _p,
                            _p, _p],
     "dvh_lm_solve_host": [_p, _p, _p, _p, _i32, _i32, _p, _p],
+    "dvh_lm_normal_sets": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _i32, _p, _i32, _f64,
+                           _p, _p, _p, _p, _p],
+    "dvh_lm_normal_sets_host": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _i32, _p, _i32,
+                                _f64, _p, _p, _p, _p],
 }
 _RESTYPES = {"dvh_last_error": C.c_char_p, "dvh_qs_curves_workspace": C.c_int64, "dvh_welch_rows_workspace": C.c_int64, "dvh_vsg_stack_workspace": C.c_int64, "dvh_sosfiltfilt_workspace": C.c_int64,
              "dvh_sosfiltfilt_plan_bytes": C.c_int64, "dvh_sos_pole_radius": C.c_double}

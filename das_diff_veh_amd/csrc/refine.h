@@ -37,18 +37,36 @@ DVH_HD int64_t slot_of(const Table& t, int s) {
   return (int64_t)p * t.n_mode + m;
 }
 
+// Whether sample s takes part.  With one observation table (kSets false) every sample does.  With observation sets
+// (dvh_lm_normal_sets) t.obs and t.sigma are the rows of the model's set and a sample is present iff its observation
+// is finite: NaN marks it absent, and nothing else of an absent sample is read.
+template <bool kSets>
+DVH_HD bool present(const Table& t, int s) {
+  return !kSets || is_finite(t.obs[s]);
+}
+DVH_HD bool sigma_ok(double sigma) { return sigma > 0.0 && is_finite(sigma); }  // asked of a set's present samples
+
+// The set's rows of set_obs and set_sigma [n_set][n_sample] in t, or false for a set outside 0 .. n_set - 1.
+DVH_HD bool select_set(Table& t, int set, int n_set) {
+  if (set < 0 || set >= n_set) return false;
+  t.obs += (int64_t)set * t.n_sample;
+  t.sigma += (int64_t)set * t.n_sample;
+  return true;
+}
+
 DVH_HD double residual(const Table& t, const double* cm, int s) {
   return (cm[slot_of(t, s)] - t.obs[s]) / t.sigma[s];
 }
 
 DVH_HD double rms_of(double sum_of_squares, int n) { return sqrt(sum_of_squares / (double)n); }
 
-// rho_i and n_i of curve i: the mean over its samples in table order.  All samples must have a slot.
+// rho_i and n_i of curve i: the mean over its present samples in table order.  All of them must have a slot.
+template <bool kSets>
 DVH_HD void curve_rms(const Table& t, const double* cm, int i, double& rho, int& n) {
   double acc = 0.0;
   n = 0;
   for (int s = 0; s < t.n_sample; ++s) {
-    if (t.curve[s] != i) continue;
+    if (!present<kSets>(t, s) || t.curve[s] != i) continue;
     const double r = residual(t, cm, s);
     acc += r * r;
     ++n;
@@ -56,11 +74,13 @@ DVH_HD void curve_rms(const Table& t, const double* cm, int i, double& rho, int&
   rho = rms_of(acc, n);
 }
 
-// f = sum_i w_i rho_i / W and W, over the curves in order.
-DVH_HD double misfit_of(const double* w, const double* rho, int n_curve, double& W) {
+// f = sum_i w_i rho_i / W and W, over the curves with a sample (n_i > 0) in order.  One observation table flags a
+// model that has a curve without a sample before it comes here; a set leaves such a curve out of both sums.
+DVH_HD double misfit_of(const double* w, const double* rho, const int* count, int n_curve, double& W) {
   double num = 0.0;
   W = 0.0;
   for (int i = 0; i < n_curve; ++i) {
+    if (count[i] == 0) continue;
     num += w[i] * rho[i];
     W += w[i];
   }

@@ -29,6 +29,10 @@ roots of ``rayleigh_modes``; ``PhaseSensitivity`` and ``group_velocity`` are the
 ``EarthModel.refine`` (dvh_lm_normal, dvh_lm_solve: csrc/refine.h) is a damped Gauss-Newton descent of the misfit from
 the swarm's models, ``InversionResult.run_best()`` or any rows of ``xs``; its objective, step and acceptance rule are
 this build's own ("Gauss-Newton refinement").
+
+``EarthModel.refine_sets`` (dvh_lm_normal_sets) is the same descent with an observation set per model: an ensemble of
+curve sets, such as one per bootstrap resample (``sets_from_ridges``), refined in one batch, and ``EnsembleResult``
+turns the refined models into a spread of profiles over depth.  The swarm itself still takes one curve set.
 """
 from __future__ import annotations
 
@@ -333,6 +337,206 @@ def lm_solve(H, g, lam, free):
     return delta, status
 
 
+# ------------------------------------------------------------------------------------------------- observation sets
+
+@dataclass
+class ObservationSets:
+    """K observation sets on one sample table (dvh_lm_normal_sets): ``table`` is ``sample_table`` of the templates,
+    ``obs`` and ``sigma`` are float64 device tensors [K, S] in its sample order, NaN in ``obs`` for an absent sample."""
+    table: SampleTable
+    obs: torch.Tensor
+    sigma: torch.Tensor
+
+    @property
+    def n_set(self):
+        return self.obs.shape[0]
+
+
+def _checked_sets(curves, data_sets, uncertainty_sets):
+    """The host half of ``observation_sets``: every check, and (obs, sigma) as NumPy [K, S] in table order."""
+    curves = list(curves)
+    if not curves:
+        raise ValueError("no curves")
+    for c in curves:
+        if not isinstance(c, Curve):
+            raise TypeError("observation sets take Curve templates")
+        c.check()
+
+    def rows(parts, what):
+        parts = list(parts)
+        if len(parts) != len(curves):
+            raise ValueError(f"{what}: one array per curve")
+        parts = [np.asarray(p, np.float64) for p in parts]
+        for p, c in zip(parts, curves):
+            if p.ndim != 2 or p.shape != (parts[0].shape[0], c.period.size):
+                raise ValueError(f"{what}: every array must be [K, len(curve.period)] with one K")
+        return np.ascontiguousarray(np.concatenate(parts, axis=1))
+
+    obs = rows(data_sets, "data_sets")
+    if obs.shape[0] < 1:
+        raise ValueError("at least one set (K >= 1)")
+    if np.isinf(obs).any():
+        raise ValueError("data must be finite, or NaN for an absent sample")
+    if uncertainty_sets is None:
+        own = [np.ones(c.period.size) if c.uncertainties is None else c.uncertainties for c in curves]
+        sigma = np.ascontiguousarray(np.broadcast_to(np.concatenate(own), obs.shape))
+    else:
+        sigma = rows(uncertainty_sets, "uncertainty_sets")
+        if sigma.shape != obs.shape:
+            raise ValueError("uncertainty_sets must have the shapes of data_sets")
+    at = np.isfinite(obs)
+    if not (np.isfinite(sigma[at]).all() and (sigma[at] > 0).all()):
+        raise ValueError("uncertainties must be positive and finite at every present sample")
+    return obs, sigma
+
+
+def _sets_on(curves, obs, sigma, dev):
+    return ObservationSets(sample_table(curves, dev), torch.from_numpy(obs).to(dev), torch.from_numpy(sigma).to(dev))
+
+
+def observation_sets(curves, data_sets, uncertainty_sets=None, device=None):
+    """K observation sets of one group of curves, as ``lm_normal_sets`` takes them -> ObservationSets.
+
+    curves            ``Curve`` templates: their period, mode, weight and uncertainties are used, their data is not
+    data_sets         a list over the curves of [K, len(curve.period)] arrays (km/s); NaN marks a sample the set lacks
+                      (a resample whose ridge has no pick there, a class without that mode's curve)
+    uncertainty_sets  None (each curve's own uncertainties, or 1, shared by all sets) or arrays of the same shapes
+
+    ValueError, before any device work, for shapes that do not match, K < 1, +-inf data or an uncertainty that is not
+    positive and finite at a present sample."""
+    obs, sigma = _checked_sets(curves, data_sets, uncertainty_sets)
+    return _sets_on(list(curves), obs, sigma, device or default_device())
+
+
+def lm_normal_sets(c, dcdp, chain, sets, model_set, rho_floor=LM_RHO_FLOOR):
+    """dvh_lm_normal_sets: ``lm_normal`` with model m scored against row ``model_set[m]`` (an int32 device tensor [M])
+    of ``sets`` (ObservationSets) -> (f [M], g [M, D], H [M, D, D], status int32 [M]) on the device."""
+    table = sets.table
+    M, P, n_mode = c.shape
+    n_layer, D = dcdp.shape[3], chain.shape[2]
+    if P != table.periods.numel() or n_mode != table.n_mode or dcdp.shape != (M, P, n_mode, n_layer, 4) or \
+            chain.shape != (M, 4 * n_layer, D):
+        raise ValueError("c [M, P, n_mode], dcdp [M, P, n_mode, n_layer, 4] and chain [M, 4 n_layer, D] on the table")
+    for t in (c, dcdp, chain):
+        if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("c, dcdp and chain must be contiguous float64 device tensors")
+    S = table.sample_curve.numel()
+    for t in (sets.obs, sets.sigma):
+        if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda or t.dim() != 2 or \
+                t.shape != (sets.n_set, S) or sets.n_set < 1:
+            raise ValueError("sets.obs and sets.sigma must be contiguous float64 device tensors [K, S], K >= 1")
+    if not isinstance(model_set, torch.Tensor) or model_set.shape != (M,) or model_set.dtype != torch.int32 or \
+            not model_set.is_contiguous() or not model_set.is_cuda:
+        raise ValueError("model_set must be a contiguous int32 device tensor [M]")
+    dev = c.device
+    f = torch.empty(M, dtype=torch.float64, device=dev)
+    g = torch.empty((M, D), dtype=torch.float64, device=dev)
+    H = torch.empty((M, D, D), dtype=torch.float64, device=dev)
+    status = torch.empty(M, dtype=torch.int32, device=dev)
+    _lib.call("dvh_lm_normal_sets", _lib.ptr(c), _lib.ptr(dcdp), _lib.ptr(chain), M, P, n_mode, n_layer, D,
+              _lib.ptr(table.sample_period), _lib.ptr(table.sample_mode), _lib.ptr(sets.obs), _lib.ptr(sets.sigma),
+              _lib.ptr(model_set), sets.n_set, _lib.ptr(table.sample_curve), S, _lib.ptr(table.curve_weight),
+              table.curve_weight.numel(), float(rho_floor), _lib.ptr(f), _lib.ptr(g), _lib.ptr(H), _lib.ptr(status),
+              _lib.stream_of(dev))
+    return f, g, H, status
+
+
+ProfileStats = namedtuple("ProfileStats", "mean std percentiles")
+
+
+@dataclass
+class EnsembleResult(RefineResult):
+    """What ``EarthModel.refine_sets`` returns: RefineResult's fields for its M starts, and
+
+    model_set  [M] int32  the set each row was refined against
+    n_set      K, the number of sets
+    """
+    model_set: np.ndarray = None
+    n_set: int = 0
+
+    def best_per_set(self):
+        """[K] row indices: per set the row of the lowest misfit among those refined against it (the first, where
+        several tie), -1 for a set whose rows are all +inf or that no row names."""
+        f = np.where(np.isnan(self.misfits), np.inf, self.misfits)
+        best = np.full(self.n_set, -1, np.int64)
+        for k in range(self.n_set):
+            rows = np.flatnonzero(self.model_set == k)
+            if rows.size and f[rows].min() < np.inf:
+                best[k] = rows[np.argmin(f[rows])]
+        return best
+
+    def profiles(self, depths_km, parameter="velocity_s"):
+        """[M, Z]: every row's layer value of ``parameter`` ("thickness", "velocity_p", "velocity_s" or "density") at
+        each depth (km).  A depth on an interface takes the layer below; below the last interface it is the
+        half-space's.  Host NumPy."""
+        col, = _parameter_columns(parameter)
+        z = np.asarray(depths_km, np.float64).reshape(-1)
+        interfaces = np.cumsum(self.models[:, :-1, 0], axis=1)                     # [M, n - 1]
+        layer = (z[None, None, :] >= interfaces[:, :, None]).sum(axis=1)           # [M, Z]
+        return np.take_along_axis(self.models[:, :, col], layer, axis=1)
+
+    def profile_stats(self, depths_km, parameter="velocity_s", percentiles=(0, 25, 50, 75, 100), rows=None):
+        """Mean [Z], standard deviation [Z] and ``np.percentile`` [len(percentiles), Z] of ``profiles`` per depth over
+        ``rows`` (default: ``best_per_set()`` without the sets that have none) -> ProfileStats."""
+        if rows is None:
+            rows = self.best_per_set()
+            rows = rows[rows >= 0]
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        if rows.size == 0:
+            raise ValueError("no rows to take the statistics over")
+        p = self.profiles(depths_km, parameter)[rows]
+        return ProfileStats(p.mean(axis=0), p.std(axis=0), np.percentile(p, percentiles, axis=0))
+
+
+def sets_from_ridges(freqs, freq_lb, freq_ub, ridges, modes, weights=None, uncertainties="std", stride=1):
+    """The bridge from ``bootstrap.bootstrap_ridges`` to ``refine_sets``: one observation set per resample.
+
+    freqs, freq_lb, freq_ub   the frequency axis (Hz) and the picked bands' bounds: band i is lb[i] <= f < ub[i]
+    ridges         a list over the picked bands of [B, n_band] ridge velocities (m/s) on that band, NaN where a
+                   resample has no pick
+    modes          the Rayleigh mode number of each band's curve
+    weights        the curves' weights (None: 1 each)
+    uncertainties  "std": each template's uncertainties are the standard deviation over the resamples per frequency
+                   (NaN ignored), a frequency where it is 0 taking the smallest positive one of its band, and None if
+                   the band has none; None: no uncertainties
+    stride         every stride-th frequency of a band is kept, counted from its first
+
+    -> (curves, data_sets): ``Curve`` templates on ascending periods (the frequencies reversed, as the notebooks build
+    theirs) with the resamples' mean as data, and per curve the [B, n] velocities in km/s.  NumPy only."""
+    if uncertainties not in ("std", None):
+        raise ValueError('uncertainties must be "std" or None')
+    freqs = np.asarray(freqs, np.float64).reshape(-1)
+    ridges = list(ridges)
+    modes = list(modes)
+    weights = [1.0] * len(ridges) if weights is None else list(weights)
+    if not len(ridges) == len(modes) == len(weights) == len(freq_lb) == len(freq_ub) or not ridges:
+        raise ValueError("one band bound, mode and weight per array of ridges, at least one")
+    if int(stride) < 1:
+        raise ValueError("stride >= 1")
+    curves, data_sets = [], []
+    for i, ridge in enumerate(ridges):
+        band = freqs[(freqs >= freq_lb[i]) & (freqs < freq_ub[i])]
+        ridge = np.asarray(ridge, np.float64)
+        if ridge.ndim != 2 or ridge.shape[0] < 1 or ridge.shape[1] != band.size or band.size == 0:
+            raise ValueError(f"ridges[{i}] must be [B, {band.size}] on its band, which must not be empty")
+        if ridge.shape[0] != np.shape(ridges[0])[0]:
+            raise ValueError("every band needs the same number of resamples")
+        keep = slice(None, None, int(stride))
+        period = (1.0 / band[keep])[::-1]
+        data = np.ascontiguousarray(ridge[:, keep][:, ::-1] / 1000.0)
+        if np.isinf(data).any() or not np.isfinite(data).any(axis=0).all():
+            raise ValueError(f"ridges[{i}] must be finite or NaN, with a pick at every frequency in some resample")
+        mean = np.nanmean(data, axis=0)
+        sigma = None
+        if uncertainties == "std":
+            sigma = np.nanstd(data, axis=0)
+            sigma = np.where(sigma > 0, sigma, sigma[sigma > 0].min()) if (sigma > 0).any() else None
+        curves.append(Curve(period, mean, int(modes[i]), "rayleigh", "phase", weight=float(weights[i]),
+                            uncertainties=sigma))
+        data_sets.append(data)
+    return curves, data_sets
+
+
 class EarthModel:
     """evodcinv's EarthModel as the notebooks use it: add(Layer) top to bottom, configure(...), invert(curves)."""
 
@@ -522,6 +726,14 @@ class EarthModel:
         The residuals use the roots after dvh_rayleigh_sens's Newton step, so ``start_misfits`` may differ from
         ``invert``'s misfit of the same model by the root refinement width over sigma (tol c / sigma per sample).
         ``profile`` records device events around the launches into ``result.timings`` (ms per iteration)."""
+        curves, xs = self._checked_problem(curves, xs, maxiter, lam0, tol, "refine()")
+        tab = sample_table(curves, default_device())
+        fields, timings = self._descend(tab, lambda c, dcdp, chain: lm_normal(c, dcdp, chain, tab), xs, maxiter, lam0,
+                                        tol, profile)
+        return RefineResult(*fields, timings=timings)
+
+    def _checked_problem(self, curves, xs, maxiter, lam0, tol, who):
+        """The argument checks of ``refine`` and ``refine_sets``, before any device work -> (curves, xs tensor)."""
         if not self._configured:
             raise ValueError("configure() the model first")
         n = len(self.layers)
@@ -536,13 +748,16 @@ class EarthModel:
         curves = list(curves)
         for c in curves:  # before any device work
             if not isinstance(c, Curve):
-                raise TypeError("refine() takes Curve objects")
+                raise TypeError(f"{who} takes Curve objects")
             c.check()
         if not 1 <= len(curves) <= LM_MAX_CURVES:
             raise ValueError(f"1 .. {LM_MAX_CURVES} curves")
-        lo_h, hi_h = self.bounds()
-        given_tensor = isinstance(xs, torch.Tensor)
-        if given_tensor:
+        return curves, self._checked_starts(xs)
+
+    def _checked_starts(self, xs):
+        """xs [M, 3 n - 1] as a float64 tensor (on whichever device it was given), inside the bounds."""
+        D = 3 * len(self.layers) - 1
+        if isinstance(xs, torch.Tensor):
             if xs.dim() != 2 or xs.shape[1] != D or xs.dtype != torch.float64:
                 raise ValueError(f"xs must be float64 [M, {D}]")
         else:
@@ -550,12 +765,19 @@ class EarthModel:
             if xs.ndim != 2 or xs.shape[1] != D:
                 raise ValueError(f"xs must be [M, {D}]")
             xs = torch.from_numpy(xs)
-        if not starts_in_bounds(xs, lo_h, hi_h):
+        if not starts_in_bounds(xs, *self.bounds()):
             raise ValueError("xs must lie inside the bounds")
-        dev = default_device()
+        return xs
+
+    def _descend(self, tab, normal, xs, maxiter, lam0, tol, profile):
+        """The loop of ``refine`` and ``refine_sets`` from the checked starts ``xs`` on the table's periods:
+        ``normal(c, dcdp, chain)`` is lm_normal on the table or lm_normal_sets on the models' sets.  -> the fields of
+        RefineResult as NumPy arrays, in its order, and the timings."""
+        dev = tab.periods.device
+        n = len(self.layers)
+        lo_h, hi_h = self.bounds()
         lo, hi = torch.from_numpy(lo_h).to(dev), torch.from_numpy(hi_h).to(dev)
         x = torch.minimum(torch.maximum(xs.to(dev), lo), hi).contiguous()
-        tab = sample_table(curves, dev)
         M, T = x.shape[0], int(maxiter)
         span = hi - lo
         free = (span > 0).to(torch.int32)
@@ -583,7 +805,7 @@ class EarthModel:
                 _lib.call("dvh_rayleigh_sens", _lib.ptr(models), M, n, _lib.ptr(tab.periods), P, _lib.ptr(c0),
                           tab.n_mode, 15, float(tol), _lib.ptr(c1), None, _lib.ptr(dcdp), _lib.stream_of(dev))
             mark(ev)
-            out = lm_normal(c1, dcdp, chain, tab)
+            out = normal(c1, dcdp, chain)
             mark(ev)
             return out
 
@@ -618,14 +840,48 @@ class EarthModel:
             marks.append(ev)
         status = (start_status & 1) | (solve_status & 2)
         host = lambda t: t.cpu().numpy()
-        res = RefineResult(host(x), host(self.models_of(x)), host(f), host(history[0]), host(history), host(accepted),
-                           host(lam), host(status), host(g), host(H))
+        fields = (host(x), host(self.models_of(x)), host(f), host(history[0]), host(history), host(accepted),
+                  host(lam), host(status), host(g), host(H))
+        timings = {}
         if profile:
             torch.cuda.synchronize(dev)
             names = ("solve_ms", "modes_ms", "sens_ms", "normal_ms", "select_ms")
-            res.timings = {name: np.array([e[k].elapsed_time(e[k + 1]) for e in marks])
-                           for k, name in enumerate(names)}
-        return res
+            timings = {name: np.array([e[k].elapsed_time(e[k + 1]) for e in marks]) for k, name in enumerate(names)}
+        return fields, timings
+
+    def refine_sets(self, curves, data_sets, xs, model_set=None, uncertainty_sets=None, maxiter=20, lam0=1e-3,
+                    tol=1e-9, profile=False):
+        """``refine`` with an observation set per model, all in one batch -> EnsembleResult.
+
+        curves, data_sets, uncertainty_sets   the K sets as ``observation_sets`` takes them: ``Curve`` templates (their
+                   period, mode, weight and uncertainties; not their data) and per curve a [K, len(period)] array of
+                   velocities (km/s), NaN where a set lacks the sample
+        xs         [M, 3 n - 1] starts inside the bounds, as ``refine`` takes them
+        model_set  int [M], the set each start is refined against; several starts may name one set.  None: M == K
+                   and start k refines set k
+
+        The loop is ``refine``'s own with dvh_lm_normal_sets in place of dvh_lm_normal: row m of every result is what
+        ``refine`` gives for start m alone against the curves of set ``model_set[m]`` (with every sample present, bit
+        for bit).  The periods and the modes scanned are the templates', whatever a set lacks; a set without a present
+        sample leaves its starts where they are, with status bit 0."""
+        curves, xs = self._checked_problem(curves, xs, maxiter, lam0, tol, "refine_sets()")
+        obs, sigma = _checked_sets(curves, data_sets, uncertainty_sets)
+        K, M = obs.shape[0], xs.shape[0]
+        if model_set is None:
+            if M != K:
+                raise ValueError(f"{M} starts for {K} sets: pass model_set")
+            model_set = np.arange(K)
+        model_set = np.asarray(model_set)
+        if model_set.shape != (M,) or model_set.dtype.kind not in "iu" or \
+                (M and not (0 <= model_set.min() and model_set.max() < K)):
+            raise ValueError(f"model_set must be int [{M}] within 0 .. {K - 1}")
+        model_set = np.ascontiguousarray(model_set, np.int32)
+        dev = default_device()
+        sets = _sets_on(curves, obs, sigma, dev)
+        at = torch.from_numpy(model_set).to(dev)
+        fields, timings = self._descend(sets.table, lambda c, dcdp, chain: lm_normal_sets(c, dcdp, chain, sets, at),
+                                        xs, maxiter, lam0, tol, profile)
+        return EnsembleResult(*fields, timings=timings, model_set=model_set, n_set=K)
 
 
 # ------------------------------------------------------------------------------------------------- sensitivities

@@ -615,6 +615,28 @@ int dvh_lm_normal(const double* c, const double* dcdp, const double* chain, int3
                   const int32_t* sample_curve, int32_t n_sample, const double* curve_weight, int32_t n_curve,
                   double rho_floor, double* out_f, double* out_g, double* out_H, int32_t* out_status, void* stream);
 
+/* dvh_lm_normal with an observation set per model: the models of one batch are each scored against their own
+ * observations.  sample_period, sample_mode, sample_curve and curve_weight are shared by the sets;
+ *   set_obs    [n_set][n_sample]  the observations of every set, NaN for a sample the set lacks
+ *   set_sigma  [n_set][n_sample]  their uncertainties
+ *   model_set  [n_model] int32    model m is scored against set model_set[m]; several models may name one set
+ * A sample is present in set k iff set_obs[k][s] is finite.  Per set, n_i counts the present samples of curve i, and a
+ * curve without one is left out of both the weighted sum and W; rho_i, a_i, j_s and rho_floor are dvh_lm_normal's over
+ * the present samples, and nothing else of an absent sample (its sigma, its slot of c and dcdp, its indices) is read.
+ * A model is flagged (f = +inf, g and H zeros, status 1) when dvh_lm_normal would flag it on its present samples, when
+ * its set has no present sample at all, when a present sample's sigma is not positive and finite, or when model_set[m]
+ * is outside 0 .. n_set - 1.  Every entry is again one sum over the present samples in table order without atomics:
+ * with every sample present the operations are dvh_lm_normal's, with some absent they are dvh_lm_normal's on the table
+ * without them (an emptied curve and its weight removed), and a model's outputs depend on nothing but its own rows.
+ * Return codes as dvh_lm_normal, and -2 also for n_set < 1 or a NULL model_set.  n_model = 0 returns 0 without a
+ * launch. */
+int dvh_lm_normal_sets(const double* c, const double* dcdp, const double* chain, int32_t n_model, int32_t n_period,
+                       int32_t n_mode, int32_t n_layer, int32_t n_param, const int32_t* sample_period,
+                       const int32_t* sample_mode, const double* set_obs, const double* set_sigma,
+                       const int32_t* model_set, int32_t n_set, const int32_t* sample_curve, int32_t n_sample,
+                       const double* curve_weight, int32_t n_curve, double rho_floor, double* out_f, double* out_g,
+                       double* out_H, int32_t* out_status, void* stream);
+
 /* The damped step of every model, one wave per model: over the parameters k with free_mask[k] != 0,
  *   A = H + lambda diag(d),  d_k = max(H_kk, 1e-12 max_j H_jj),   A delta = -g
  * by a float64 Cholesky factorisation of the packed lower triangle in LDS and two triangular solves; only the lower
@@ -628,9 +650,15 @@ int dvh_lm_normal(const double* c, const double* dcdp, const double* chain, int3
 int dvh_lm_solve(const double* H, const double* g, const double* lambda, const int32_t* free_mask, int32_t n_model,
                  int32_t n_param, double* out_delta, int32_t* out_status, void* stream);
 
-/* dvh_lm_normal and dvh_lm_solve on the CPU over host memory, from the same header (csrc/refine.h) and in the same
- * order of operations; no device is touched.  They pin the arithmetic where there is no GPU and are no fallback:
- * nothing refines models with them.  Arguments, outputs and return codes as above. */
+/* dvh_lm_normal, dvh_lm_normal_sets and dvh_lm_solve on the CPU over host memory, from the same header
+ * (csrc/refine.h) and in the same order of operations; no device is touched.  They pin the arithmetic where there is no
+ * GPU and are no fallback: nothing refines models with them.  Arguments, outputs and return codes as above. */
+int dvh_lm_normal_sets_host(const double* c, const double* dcdp, const double* chain, int32_t n_model,
+                            int32_t n_period, int32_t n_mode, int32_t n_layer, int32_t n_param,
+                            const int32_t* sample_period, const int32_t* sample_mode, const double* set_obs,
+                            const double* set_sigma, const int32_t* model_set, int32_t n_set,
+                            const int32_t* sample_curve, int32_t n_sample, const double* curve_weight, int32_t n_curve,
+                            double rho_floor, double* out_f, double* out_g, double* out_H, int32_t* out_status);
 int dvh_lm_normal_host(const double* c, const double* dcdp, const double* chain, int32_t n_model, int32_t n_period,
                        int32_t n_mode, int32_t n_layer, int32_t n_param, const int32_t* sample_period,
                        const int32_t* sample_mode, const double* sample_obs, const double* sample_sigma,
