@@ -762,8 +762,9 @@ __global__ __launch_bounds__(256) void vsg_pivot_table_kernel(VsgArgs A, float2*
 
 // ------------------------------------------------------------------------------------------------
 // The validated stack launch: the correlation waves and the window validity scan (vsg_scan.h) in one kernel.
-// correlation waves raise their issue priority while they correlate (scan waves stay at 0): the correlation is the
-// critical path; 1 / 2 / 3 all measured 127.7 k -> 136 k windows/s on synth10k
+// correlation waves raise their issue priority while they correlate (scan waves stay at 0);
+// 1 / 2 / 3 all measured 127.7 k -> 136 k windows/s on synth10k (at
+// 7 + 1 waves, when the correlation was the launch's longer half; not re-measured for the 5 + 3 shape)
 constexpr int kCorrPrio = 2;
 
 // The row tasks of a stack launch: frequency-domain stacking with the engine's exact (N = w) transforms, or
@@ -917,6 +918,7 @@ struct VsgEngine {
   int waves;
   size_t lds;
   VStack v;                  // validated launch
+  VStack vs;                 // its shape for a launch held by its scan (pick_vstack), if the engine has one
   const void* table;         // pivot-slice table kernel (the fused-stage engines), or nullptr
   size_t table_lds;          // the engine's block tables + 4 waves' buffers (EngP1024's padded buffer A included)
   int64_t table_pass_bytes;  // table workspace per pass: the entries' spectra and their (start, nwin) head
@@ -924,7 +926,7 @@ struct VsgEngine {
 };
 
 template <class E>
-static VsgEngine engine_row(VStack v = VStack{}, bool span = false) {
+static VsgEngine engine_row(VStack v = VStack{}, bool span = false, VStack vs = VStack{}) {
   VsgEngine d{};
   d.nfft = E::NFFT;
   d.exact = E::kExact;
@@ -935,6 +937,7 @@ static VsgEngine engine_row(VStack v = VStack{}, bool span = false) {
   d.waves = E::kWaves;
   d.lds = E::kBlockBytes + E::kWaves * E::kWaveBytes;
   d.v = v;
+  d.vs = vs;
   if constexpr (E::kFused) {
     d.table = (const void*)vsg_pivot_table_kernel<E>;
     d.table_lds = E::kBlockBytes + 4 * E::kWaveBytes;
@@ -945,9 +948,23 @@ static VsgEngine engine_row(VStack v = VStack{}, bool span = false) {
 }
 
 // Validated launch shapes.  EngF500: blocks of 7 correlation + 1 scan waves, 2 blocks per CU (4 waves per SIMD, the
-// registers sized for it by the launch bounds).  EngP1024: 7 + 1 waves, one block per CU (LDS, registers), its scan
+// registers sized for it by the launch bounds); a launch held by its scan runs 5 + 3 instead (pick_vstack).  With the
+// covered-span scan and the 10 x 10 x 5 engine synth10k is such a launch: 12.49-12.51 ms at 7 + 1 -> 11.09 ms at
+// 5 + 3 (72.7 GB: 6.56 TB/s); weights, held by its correlation, would pay 1-3 % (1.20-1.21 -> 1.22-1.25 ms) and
+// stays at 7 + 1 (profiles/eng500_wave_mix.json).  The correlation waves' task stride is grid x the
+// correlation waves per block: 6 + 2 and 4 + 4 give strides of 3 and 2 rows modulo synth10k's 1 023 gather rows, a
+// wave then stays among rows of one cost, and both measured slower than 7 + 1 (13.3-13.5 ms).
+// EngP1024: 7 + 1 waves, one block per CU (LDS, registers), its scan
 // waves keeping 32 loads per lane in flight (w = 499 synth10k launch 14.70 vs 15.08 ms at 16, 14.92 at 48).
 constexpr int kVsFft = 7, kVsScan = 1, kVsBpc = 2, kVsOcc = 4;
+constexpr int kVsHeavyFft = 5, kVsHeavyScan = 3;
+// A launch takes the scan-heavy shape when it scans at least this many window bytes per (pass, gather row) it
+// correlates.  One (pass, row) costs the 14 correlation waves of a CU 3.4 ns of the launch on synth10k (corr7 7.0 ms,
+// rows served by the pivot-slice table) and 5.1-5.4 ns on weights (corr7 0.93-0.97 ms, 48 rows); in those times a
+// 6.4 TB/s stream moves 22 and 33-34 KB: below the first a launch is held by its correlation whatever its rows cost,
+// above the second by its scan.  The entry point does not see what a launch's rows cost, so the threshold sits
+// between the two workloads: synth10k scans 32.8 KB per (pass, row), weights 27.5 KB.
+constexpr int64_t kVsHeavyBytes = 30000;
 constexpr int kVsSpan = 11;  // the covered-span scan's loads per lane in flight in the EngF500 launch: the most without
                              // spills (12 spill; 11 vs 8: synth10k 13.06 vs 13.09-13.13 ms, profiles/r6_ab)
 constexpr int kP1Fft = 7, kP1Scan = 1, kP1Depth = 32;
@@ -960,7 +977,8 @@ constexpr int kP1Fft = 7, kP1Scan = 1, kP1Depth = 32;
 static const VsgEngine* engine_for(int w) {
   static const VsgEngine rows[] = {
       engine_row<EngStockham<250, false>>(),
-      engine_row<EngF500>(vstack<EngF500, kVsFft, kVsScan, kVsOcc, kScanDepth, kVsSpan>(kVsBpc), /*span=*/true),
+      engine_row<EngF500>(vstack<EngF500, kVsFft, kVsScan, kVsOcc, kScanDepth, kVsSpan>(kVsBpc), /*span=*/true,
+                          vstack<EngF500, kVsHeavyFft, kVsHeavyScan, kVsOcc, kScanDepth, kVsSpan>(kVsBpc)),
       engine_row<EngStockham<1000, false>>(),
       engine_row<EngStockham<512, true>>(vstack<EngStockham<512, true>, 7, 1, 2>(1)),
       engine_row<EngP1024>(vstack<EngP1024, kP1Fft, kP1Scan, 2, kP1Depth>(1)),
@@ -969,6 +987,14 @@ static const VsgEngine* engine_for(int w) {
   for (const VsgEngine& e : rows)  // the exact rows first
     if (e.exact ? w == e.nfft : 2 * w - 1 <= e.nfft) return &e;
   return nullptr;
+}
+
+// The validated launch shape of one launch: the engine's scan-heavy one when it has one and the launch scans at least
+// kVsHeavyBytes of windows (n_win of n_ch x n_t floats) per (pass, gather row) it correlates.
+static const VStack& pick_vstack(const VsgEngine& e, int64_t n_win, int64_t n_ch, int64_t n_t, int64_t n_pass,
+                                 int64_t R) {
+  const bool heavy = e.vs.fn && n_win * n_ch * n_t * (int64_t)sizeof(float) >= kVsHeavyBytes * n_pass * R;
+  return heavy ? e.vs : e.v;
 }
 
 static int check_common(const VsgArgs& A) {
@@ -1027,6 +1053,14 @@ using namespace dvh;
 DVH_API int dvh_vsg_fft_length(int32_t w) {
   const VsgEngine* e = engine_for(w);
   return e ? e->nfft : 0;
+}
+
+DVH_API int dvh_vsg_stack_validated_waves(int32_t w, int32_t n_win, int32_t n_ch, int32_t n_t, int32_t n_pass,
+                                          int32_t R) {
+  const VsgEngine* e = engine_for(w);
+  if (!e || !e->v.fn) return 0;
+  const VStack& v = pick_vstack(*e, n_win, n_ch, n_t, n_pass, R);
+  return 16 * v.fft + v.scan;
 }
 
 DVH_API int dvh_window_sumsq(const float* win, int64_t pass_stride, int64_t ch_stride, int32_t n_pass, int32_t n_ch,
@@ -1101,7 +1135,7 @@ DVH_API int dvh_vsg_stack_validated(const float* win, int64_t pass_stride, int64
   if (e.v.fn) {
     if (tab)
       if (int rc = launch_table(e, A, tab, s)) return rc;
-    const VStack& v = e.v;
+    const VStack& v = pick_vstack(e, S.n_win, n_ch, n_t, n_pass, R);
     const int64_t need = ((int64_t)n_chunk * R + v.fft - 1) / v.fft;
     const int grid = (int)(need < v.bpc * cu_count() ? (need > 0 ? need : 1) : v.bpc * cu_count());
     void* args[] = {&A, &scales, &order, &chunk_tab, &n_chunk, &weight, &stack, (void*)&S, &vflag, &counter, &tab, &span};

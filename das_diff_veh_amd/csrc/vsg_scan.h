@@ -6,7 +6,8 @@
 // an all-zero window, makes the whole gather NaN (norm / norm_amp divide by a NaN or zero maximum
 // afterwards), and so its class mean.  Deciding that needs every sample of the window, 4x - 130x the
 // bytes the correlations read.  In the validated stack launch, besides the correlation waves, one
-// wave per block streams the windows (16 x 16-byte loads per lane in flight) and keeps the maximum
+// to three waves per block (the launch's shape: dvh_vsg.hip, pick_vstack) stream the windows (16 x 16-byte loads per
+// lane in flight) and keep the maximum
 // of |x| as a bit pattern, max(bits & 0x7fffffff): >= 0x7f800000 means a NaN / inf, 0 means all
 // zero.  Work is pulled in units of kScanRows channel rows from a global counter, by the scan waves
 // from the start and by the correlation waves once their row tasks are done, so the HBM-bound scan

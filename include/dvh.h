@@ -124,6 +124,12 @@ int dvh_vsg_stack_validated(const float* win, int64_t pass_stride, int64_t ch_st
  * it; with spec_ws == NULL the stack entries run the per-sub-window engine instead. */
 int64_t dvh_vsg_stack_workspace(int32_t n_pass, int32_t w);
 
+/* The block shape dvh_vsg_stack_validated launches for window length w when it scans n_win windows of
+ * n_ch x n_t samples and correlates n_pass passes of R gather rows: 16 x correlation waves + scan waves
+ * per block (w = 500: 7 + 1, or 5 + 3 for a launch held by its scan), 0 when the scan is a launch of
+ * its own.  Launches nothing. */
+int dvh_vsg_stack_validated_waves(int32_t w, int32_t n_win, int32_t n_ch, int32_t n_t, int32_t n_pass, int32_t R);
+
 /* ---------------------------------------------------------------- dispersion (map_fv)
  * Gathers data[B][nch][nt] (strides in elements).  Only the FK bins the (f, k = f / v) queries
  * touch are formed: n_fb frequency bins (twiddles wt[nt][2 * n_fb] = cos | -sin) and n_kb

@@ -1,7 +1,8 @@
 """Stack-launch breakdown on one batch of a bench workload (default synth10k, BASELINE configs[2]), HIP-event timed:
 
     fused      vsg_stack_validated (correlation + whole-window scan in one launch, the bench's kernel)
-    corr7      the same launch with a one-window scan: the correlation alone in the fused launch's layout
+    corr7      the same launch with a one-window scan: the correlation alone in the persistent layout (the entry
+               point picks the block shape from the scanned bytes: one window is 7 correlation + 1 scan waves)
     corr       vsg_stack (the correlation alone, 4 waves per block)
     sumsq      window_sumsq of the batch (the validity as its own streaming pass)
 
