@@ -89,9 +89,13 @@ SIGNATURES = {
                            _p, _p, _p, _p, _p],
     "dvh_lm_normal_sets_host": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _i32, _p, _i32,
                                 _f64, _p, _p, _p, _p],
+    "dvh_lm_solve_chain_workspace": [_i32, _i32],
+    "dvh_lm_solve_chain": [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p],
+    "dvh_lm_solve_chain_host": [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p],
 }
 _RESTYPES = {"dvh_last_error": C.c_char_p, "dvh_qs_curves_workspace": C.c_int64, "dvh_welch_rows_workspace": C.c_int64, "dvh_vsg_stack_workspace": C.c_int64, "dvh_sosfiltfilt_workspace": C.c_int64,
-             "dvh_sosfiltfilt_plan_bytes": C.c_int64, "dvh_sos_pole_radius": C.c_double}
+             "dvh_sosfiltfilt_plan_bytes": C.c_int64, "dvh_sos_pole_radius": C.c_double,
+             "dvh_lm_solve_chain_workspace": C.c_int64}
 
 _lock = threading.Lock()
 _lib = None

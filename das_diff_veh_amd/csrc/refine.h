@@ -126,5 +126,50 @@ DVH_HD double chol_reduce(const double* L, int i, int j) {
 }
 DVH_HD bool pivot_ok(double v) { return v > 0.0 && is_finite(v); }
 
+// ---- chains of models (dvh_lm_solve_chain; DESIGN.md, "Laterally constrained refinement") ----
+// Position k of a chain has the diagonal block A_k and, towards k + 1, the block B_k = -w_k diag(mu).  The block
+// Cholesky keeps per position the packed lower triangle L_k and X_k = B_k L_k^-T, which is upper triangular and is
+// packed as its transpose U: U[tri(p, i)] = X_k[i][p], i <= p.  Every sum below runs in index order in one thread.
+
+// q_k[d] = mu_d [ w_{k-1} (u_k - u_{k-1}) - w_k (u_{k+1} - u_k) ], a term that has no neighbour left out.
+DVH_HD double coupling_gradient(double mu, bool has_left, double w_left, double u_left, bool has_right, double w_right,
+                                double u_right, double u_here) {
+  double t = 0.0;
+  if (has_left) t += w_left * (u_here - u_left);
+  if (has_right) t -= w_right * (u_right - u_here);
+  return mu * t;
+}
+// A_k's diagonal entry from dvh_lm_solve's damped one; a link that does not exist is passed as 0.
+DVH_HD double coupled_diagonal(double damped, double w_left, double w_right, double mu) {
+  return damped + (w_left + w_right) * mu;
+}
+DVH_HD double link_entry(double w, double mu) { return -(w * mu); }  // B_k's diagonal
+DVH_HD double chain_rhs(double g, double q) { return 0.0 - (g + q); }
+
+// (i, j), j <= i, of S_k = A_k - X_{k-1} X_{k-1}^T from v = A_k's entry and U of position k - 1.
+DVH_HD double schur_reduce(double v, const double* U, int i, int j, int n) {
+  for (int p = i; p < n; ++p) v -= U[tri(p, i)] * U[tri(p, j)];
+  return v;
+}
+// Entry i of r_k - X_{k-1} y_{k-1}.
+DVH_HD double carry_forward(double r, const double* U, const double* y_before, int i, int n) {
+  for (int p = i; p < n; ++p) r -= U[tri(p, i)] * y_before[p];
+  return r;
+}
+// Row i of X_k L_k^T = B_k by substitution along the row, b = B_k's entry (i, i); written into U.
+DVH_HD void link_row(const double* L, double* U, int i, int n, double b) {
+  U[tri(i, i)] = b / L[tri(i, i)];
+  for (int j = i + 1; j < n; ++j) {
+    double s = 0.0;
+    for (int p = i; p < j; ++p) s -= U[tri(p, i)] * L[tri(j, p)];
+    U[tri(j, i)] = s / L[tri(j, j)];
+  }
+}
+// Entry p of y_k - X_k^T delta_{k+1}.
+DVH_HD double carry_back(double t, const double* U, const double* delta_after, int p) {
+  for (int i = 0; i <= p; ++i) t -= U[tri(p, i)] * delta_after[i];
+  return t;
+}
+
 }  // namespace refine
 }  // namespace dvh

@@ -33,6 +33,11 @@ this build's own ("Gauss-Newton refinement").
 ``EarthModel.refine_sets`` (dvh_lm_normal_sets) is the same descent with an observation set per model: an ensemble of
 curve sets, such as one per bootstrap resample (``sets_from_ridges``), refined in one batch, and ``EnsembleResult``
 turns the refined models into a spread of profiles over depth.  The swarm itself still takes one curve set.
+
+``EarthModel.refine_section`` (dvh_lm_solve_chain) refines ordered sets, the pivots along the fibre or the days of a
+time lapse, as chains: neighbouring models are tied by first differences in the unit cube, a chain's step is one
+block-tridiagonal solve, and ``SectionResult.section`` lays the profiles out as [chain, position, depth] (DESIGN.md,
+"Laterally constrained refinement").
 """
 from __future__ import annotations
 
@@ -337,6 +342,47 @@ def lm_solve(H, g, lam, free):
     return delta, status
 
 
+def lm_solve_chain(H, g, u, lam, free, mu, link, chain_len):
+    """dvh_lm_solve_chain: the damped step of C = M / chain_len chains of models tied by first differences (DESIGN.md,
+    "Laterally constrained refinement") -> (delta [M, D], status int32 [C]).  Rows c chain_len + k of H [M, D, D],
+    g [M, D] and u [M, D] (the unit cube) are the positions of chain c; lam is [C], free int32 [D], mu [D] and link
+    [C, chain_len - 1] are the coupling and the link weights, all device tensors (mu and link >= 0: not checked
+    here)."""
+    M, D = g.shape
+    L = int(chain_len)
+    if L < 1 or M % L:
+        raise ValueError(f"{M} rows are not chains of {chain_len}")
+    C = M // L
+    if H.shape != (M, D, D) or u.shape != (M, D) or lam.shape != (C,) or free.shape != (D,) or \
+            free.dtype != torch.int32 or mu.shape != (D,) or link.shape != (C, L - 1):
+        raise ValueError("H [M, D, D], g and u [M, D], lam [C], int32 free [D], mu [D] and link [C, chain_len - 1]")
+    for t in (H, g, u, lam, free, mu, link):
+        if not t.is_contiguous() or not t.is_cuda or (t is not free and t.dtype != torch.float64):
+            raise ValueError("H, g, u, lam, mu and link must be contiguous float64 device tensors")
+    delta = torch.empty_like(g)
+    status = torch.empty(C, dtype=torch.int32, device=g.device)
+    work = torch.empty(max(_lib.load().dvh_lm_solve_chain_workspace(M, D) // 8, 1), dtype=torch.float64,
+                       device=g.device)
+    if link.numel() == 0:  # chains of one position have no link, and an empty tensor has no address
+        link = link.new_zeros(1)
+    _lib.call("dvh_lm_solve_chain", _lib.ptr(H), _lib.ptr(g), _lib.ptr(u), _lib.ptr(lam), _lib.ptr(free),
+              _lib.ptr(mu), _lib.ptr(link), C, L, D, _lib.ptr(work), _lib.ptr(delta), _lib.ptr(status),
+              _lib.stream_of(g.device))
+    return delta, status
+
+
+def coupling_terms(u, mu, link):
+    """The penalty and its gradient of chains in the unit cube (torch ops on any device): u [C, L, D], mu [D] (0 for a
+    parameter that is not coupled, fixed ones included), link [C, L - 1] -> (P [C], q [C, L, D]) with
+    P_c = 1/2 sum_k w_{c,k} sum_d mu_d (u_{k+1,d} - u_{k,d})^2 and q = dP/du."""
+    du = u[:, 1:] - u[:, :-1]
+    t = (link[:, :, None] * mu) * du
+    q = torch.zeros_like(u)
+    q[:, 1:] += t
+    q[:, :-1] -= t
+    return 0.5 * (t * du).sum(dim=(1, 2)), q
+
+
 # ------------------------------------------------------------------------------------------------- observation sets
 
 @dataclass
@@ -486,6 +532,72 @@ class EnsembleResult(RefineResult):
             raise ValueError("no rows to take the statistics over")
         p = self.profiles(depths_km, parameter)[rows]
         return ProfileStats(p.mean(axis=0), p.std(axis=0), np.percentile(p, percentiles, axis=0))
+
+
+@dataclass
+class SectionResult(EnsembleResult):
+    """What ``EarthModel.refine_section`` returns: EnsembleResult's fields for the M = n_chain chain_len rows (row
+    c chain_len + k is position k of chain c), with ``accepted`` and ``lam`` of a chain repeated over its rows,
+    ``gradient`` and ``hessian`` the data terms g_k and H_k (0 at a gap), and
+
+    n_chain, chain_len   C and L
+    coupling             [D] mu as given (a scalar broadcast); a fixed parameter takes no part whatever its mu
+    link_weights         [C, L - 1] w
+    gap                  [M] bool  rows whose set has no present sample
+    objective, penalty   [C]  Phi_c and P_c at ``xs``
+    objective_history    [maxiter + 1, C]  the kept Phi_c after every iteration; row 0 is the starts'
+    chain_status         [C] int32  bit 0: the chain was not alive (a non-gap row starts at f = +inf, or every row is a
+                         gap) and its rows are returned as given; bit 1: the last damped system had no positive pivot
+
+    A gap row of a live chain has ``misfits`` (and its column of ``history``) NaN and status bit 2 (value 4): it is
+    carried by its neighbours.  The rows of a chain that is not alive are what ``refine_sets`` returns for them."""
+    n_chain: int = 0
+    chain_len: int = 0
+    coupling: np.ndarray = None
+    link_weights: np.ndarray = None
+    gap: np.ndarray = None
+    objective: np.ndarray = None
+    penalty: np.ndarray = None
+    objective_history: np.ndarray = None
+    chain_status: np.ndarray = None
+
+    def section(self, depths_km, parameter="velocity_s"):
+        """[C, L, Z]: ``profiles`` with the rows laid out as chains and positions."""
+        p = self.profiles(depths_km, parameter)
+        return p.reshape(self.n_chain, self.chain_len, p.shape[1])
+
+
+def _checked_model_set(model_set, M, K):
+    """``refine_sets``' model_set [M] within 0 .. K - 1 as int32 (None: M == K, start k on set k)."""
+    if model_set is None:
+        if M != K:
+            raise ValueError(f"{M} starts for {K} sets: pass model_set")
+        model_set = np.arange(K)
+    model_set = np.asarray(model_set)
+    if model_set.shape != (M,) or model_set.dtype.kind not in "iu" or \
+            (M and not (0 <= model_set.min() and model_set.max() < K)):
+        raise ValueError(f"model_set must be int [{M}] within 0 .. {K - 1}")
+    return np.ascontiguousarray(model_set, np.int32)
+
+
+def _checked_chains(M, D, chain_len, coupling, link_weights):
+    """The chain arguments of ``refine_section`` -> (C, L, mu [D], w [C, L - 1]) as NumPy, or ValueError."""
+    L = M if chain_len is None else int(chain_len)
+    if L < 1 or M % L:
+        raise ValueError(f"{M} rows are not chains of chain_len = {chain_len}")
+    C = M // L
+    mu = np.asarray(coupling, np.float64)
+    if mu.shape not in ((), (D,)):
+        raise ValueError(f"coupling must be a scalar or [{D}]")
+    mu = np.array(np.broadcast_to(mu, (D,)))  # a copy: broadcast views are read-only
+    w = np.ones((C, L - 1)) if link_weights is None else np.asarray(link_weights, np.float64)
+    if w.shape not in ((L - 1,), (C, L - 1)):
+        raise ValueError(f"link_weights must be [{L - 1}] or [{C}, {L - 1}]")
+    w = np.array(np.broadcast_to(w, (C, L - 1)))
+    for name, a in (("coupling", mu), ("link_weights", w)):
+        if not (np.isfinite(a).all() and (a >= 0).all()):
+            raise ValueError(f"{name} must be finite and not negative")
+    return C, L, mu, w
 
 
 def sets_from_ridges(freqs, freq_lb, freq_ub, ridges, modes, weights=None, uncertainties="std", stride=1):
@@ -769,16 +881,17 @@ class EarthModel:
             raise ValueError("xs must lie inside the bounds")
         return xs
 
-    def _descend(self, tab, normal, xs, maxiter, lam0, tol, profile):
-        """The loop of ``refine`` and ``refine_sets`` from the checked starts ``xs`` on the table's periods:
-        ``normal(c, dcdp, chain)`` is lm_normal on the table or lm_normal_sets on the models' sets.  -> the fields of
-        RefineResult as NumPy arrays, in its order, and the timings."""
+    def _evaluator(self, tab, normal, xs, tol, profile):
+        """What the loops of ``_descend`` and ``_descend_section`` share: the starts clamped into the cube on the
+        table's device, lo, hi, span and the int32 free mask there, ``mark(ev)`` (a device event appended to ev when
+        profiling) and ``normal_at(x, ev)``: models and chain of x, dvh_rayleigh_modes with ``invert``'s scan,
+        dvh_rayleigh_sens and ``normal(c, dcdp, chain)``, with events between them."""
         dev = tab.periods.device
         n = len(self.layers)
         lo_h, hi_h = self.bounds()
         lo, hi = torch.from_numpy(lo_h).to(dev), torch.from_numpy(hi_h).to(dev)
         x = torch.minimum(torch.maximum(xs.to(dev), lo), hi).contiguous()
-        M, T = x.shape[0], int(maxiter)
+        M = x.shape[0]
         span = hi - lo
         free = (span > 0).to(torch.int32)
         c_min = 0.8 * min(l.velocity_s[0] for l in self.layers)
@@ -787,7 +900,6 @@ class EarthModel:
         count = torch.empty((M, P), dtype=torch.int32, device=dev)
         c1 = torch.empty_like(c0)
         dcdp = torch.empty((M, P, tab.n_mode, n, 4), dtype=torch.float64, device=dev)
-        marks = []
 
         def mark(ev):
             if profile:
@@ -809,6 +921,16 @@ class EarthModel:
             mark(ev)
             return out
 
+        return x, lo, hi, span, free, mark, normal_at
+
+    def _descend(self, tab, normal, xs, maxiter, lam0, tol, profile):
+        """The loop of ``refine`` and ``refine_sets`` from the checked starts ``xs`` on the table's periods:
+        ``normal(c, dcdp, chain)`` is lm_normal on the table or lm_normal_sets on the models' sets.  -> the fields of
+        RefineResult as NumPy arrays, in its order, and the timings."""
+        dev = tab.periods.device
+        x, lo, hi, span, free, mark, normal_at = self._evaluator(tab, normal, xs, tol, profile)
+        M, T = x.shape[0], int(maxiter)
+        marks = []
         u = torch.where(span > 0, (x - lo) / torch.where(span > 0, span, torch.ones_like(span)), torch.zeros_like(x))
         u = torch.clamp(u, 0.0, 1.0)
         f, g, H, start_status = normal_at(x, [])
@@ -867,21 +989,131 @@ class EarthModel:
         curves, xs = self._checked_problem(curves, xs, maxiter, lam0, tol, "refine_sets()")
         obs, sigma = _checked_sets(curves, data_sets, uncertainty_sets)
         K, M = obs.shape[0], xs.shape[0]
-        if model_set is None:
-            if M != K:
-                raise ValueError(f"{M} starts for {K} sets: pass model_set")
-            model_set = np.arange(K)
-        model_set = np.asarray(model_set)
-        if model_set.shape != (M,) or model_set.dtype.kind not in "iu" or \
-                (M and not (0 <= model_set.min() and model_set.max() < K)):
-            raise ValueError(f"model_set must be int [{M}] within 0 .. {K - 1}")
-        model_set = np.ascontiguousarray(model_set, np.int32)
+        model_set = _checked_model_set(model_set, M, K)
         dev = default_device()
         sets = _sets_on(curves, obs, sigma, dev)
         at = torch.from_numpy(model_set).to(dev)
         fields, timings = self._descend(sets.table, lambda c, dcdp, chain: lm_normal_sets(c, dcdp, chain, sets, at),
                                         xs, maxiter, lam0, tol, profile)
         return EnsembleResult(*fields, timings=timings, model_set=model_set, n_set=K)
+
+
+    def _descend_section(self, tab, normal, xs, gap, mu, link, L, maxiter, lam0, tol, profile):
+        """The loop of ``refine_section`` beside ``_descend``: the same evaluation of the trial points,
+        dvh_lm_solve_chain for the step and acceptance per chain by Phi_c.  gap [M] bool, mu [D] and link [C, L - 1] are device tensors.
+        -> the fields of RefineResult in its order, the chain fields as a dict, and the timings."""
+        dev = tab.periods.device
+        x, lo, hi, span, free, mark, normal_at = self._evaluator(tab, normal, xs, tol, profile)
+        M, T, D = x.shape[0], int(maxiter), x.shape[1]
+        C = M // L
+        marks = []
+        mu = torch.where(span > 0, mu, torch.zeros_like(mu))  # the penalty runs over the free parameters
+        rows = lambda per_chain: per_chain.repeat_interleave(L)
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+
+        def without_gaps(f, g, H):  # a gap contributes f = 0, g = 0, H = 0 (lm_normal_sets flags it: +inf, status 1)
+            return (torch.where(gap, zero, f), torch.where(gap[:, None], zero, g),
+                    torch.where(gap[:, None, None], zero, H))
+
+        def objective(f_data, u):
+            P, _ = coupling_terms(u.view(C, L, D), mu, link)
+            return f_data.view(C, L).sum(dim=1) + P, P
+
+        u = torch.where(span > 0, (x - lo) / torch.where(span > 0, span, torch.ones_like(span)), torch.zeros_like(x))
+        u = torch.clamp(u, 0.0, 1.0)
+        f, g, H, start_status = normal_at(x, [])
+        fd, g, H = without_gaps(f, g, H)
+        ok = (start_status == 0) | gap
+        alive = ok.view(C, L).all(dim=1) & (~gap).view(C, L).any(dim=1)
+        phi, pen = objective(fd, u)
+        lam = torch.full((C,), float(lam0), dtype=torch.float64, device=dev)
+        history = torch.empty((T + 1, M), dtype=torch.float64, device=dev)
+        phi_history = torch.empty((T + 1, C), dtype=torch.float64, device=dev)
+        accepted = torch.empty((T, C), dtype=torch.bool, device=dev)
+        history[0], phi_history[0] = f, phi
+        solve_status = torch.zeros(C, dtype=torch.int32, device=dev)
+        ten = torch.tensor(10.0, dtype=torch.float64, device=dev)
+        for it in range(T):
+            ev = []
+            mark(ev)
+            delta, solve_status = lm_solve_chain(H, g, u, lam, free, mu, link, L)
+            u_t = torch.clamp(u + delta, 0.0, 1.0)
+            x_t = torch.minimum(torch.addcmul(lo, u_t, span), hi)
+            f_t, g_t, H_t, _ = normal_at(x_t, ev)
+            fd_t, g_t, H_t = without_gaps(f_t, g_t, H_t)
+            phi_t, pen_t = objective(fd_t, u_t)
+            take_c = (phi_t < phi) & alive  # +inf at a non-gap position never is lower
+            take = rows(take_c)
+            f = torch.where(take, f_t, f)
+            fd = torch.where(take, fd_t, fd)
+            g = torch.where(take[:, None], g_t, g)
+            H = torch.where(take[:, None, None], H_t, H)
+            u = torch.where(take[:, None], u_t, u)
+            x = torch.where(take[:, None], x_t, x)
+            phi = torch.where(take_c, phi_t, phi)
+            pen = torch.where(take_c, pen_t, pen)
+            lam = torch.where(take_c, torch.clamp(lam / ten, min=LM_LAMBDA_MIN),
+                              torch.clamp(lam * ten, max=LM_LAMBDA_MAX))
+            history[it + 1], phi_history[it + 1] = f, phi
+            accepted[it] = take_c
+            mark(ev)
+            marks.append(ev)
+        carried = gap & rows(alive)  # a gap row of a live chain: no misfit of its own
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        history = torch.where(carried, nan, history)
+        chain_status = ((~alive).to(torch.int32)) | (solve_status & 2)
+        status = torch.where(carried, torch.full_like(start_status, 4), start_status & 1) | rows(solve_status & 2)
+        host = lambda t: t.cpu().numpy()
+        fields = (host(x), host(self.models_of(x)), host(history[T]), host(history[0]), host(history),
+                  host(accepted.repeat_interleave(L, dim=1)), host(rows(lam)), host(status), host(g), host(H))
+        more = dict(objective=host(phi), penalty=host(pen), objective_history=host(phi_history),
+                    chain_status=host(chain_status))
+        timings = {}
+        if profile:
+            torch.cuda.synchronize(dev)
+            names = ("solve_ms", "modes_ms", "sens_ms", "normal_ms", "select_ms")
+            timings = {name: np.array([e[k].elapsed_time(e[k + 1]) for e in marks]) for k, name in enumerate(names)}
+        return fields, more, timings
+
+    def refine_section(self, curves, data_sets, xs, chain_len=None, coupling=1.0, link_weights=None, model_set=None,
+                       uncertainty_sets=None, maxiter=20, lam0=1e-3, tol=1e-9, profile=False):
+        """``refine_sets`` with neighbouring rows tied together: a laterally constrained refinement of chains of models
+        into a section -> SectionResult.
+
+        curves, data_sets, xs, model_set, uncertainty_sets, maxiter, lam0, tol, profile   as ``refine_sets`` takes them
+        chain_len     L: rows c L + k, k = 0 .. L - 1, of ``xs`` are the positions of chain c, in order along the fibre
+                      (or in time).  None: one chain of all rows
+        coupling      mu >= 0, a scalar or [3 n - 1] in the unit cube of the bounds: the weight of the squared first
+                      difference of each parameter between neighbours.  0 leaves a parameter free of its neighbours
+        link_weights  w >= 0, [L - 1] (every chain's) or [C, L - 1], default 1: the weight of each link.  0 cuts the
+                      chain there; 1 / spacing^2 serves unevenly spaced positions
+
+        Per chain the objective is Phi_c = sum_k f_k + 1/2 sum_k w_k sum_d mu_d (u_{k+1,d} - u_{k,d})^2 over the rows
+        with data and the free parameters ("Laterally constrained refinement").  A row whose set has no
+        present sample is a gap: it adds nothing to Phi_c and is carried by its neighbours through the penalty.  The
+        step of a whole chain is one block-tridiagonal solve (dvh_lm_solve_chain) with one damping per chain; the trial
+        of the whole chain is taken iff its Phi_c is lower, and lambda_c follows ``refine``'s rule.  A chain with a
+        non-gap row whose start has f = +inf, or without any data, is returned as given (status bit 0).  With
+        ``chain_len=1`` every row is ``refine_sets``' bit for bit.  Nothing is read back before the end.
+
+        ValueError, before any device work: what ``refine_sets`` raises; M not a multiple of ``chain_len``; a coupling
+        or link weight that is negative or not finite; a coupling that is neither a scalar nor [3 n - 1]; link weights
+        that are neither [L - 1] nor [C, L - 1]."""
+        curves, xs = self._checked_problem(curves, xs, maxiter, lam0, tol, "refine_section()")
+        obs, sigma = _checked_sets(curves, data_sets, uncertainty_sets)
+        K, M = obs.shape[0], xs.shape[0]
+        model_set = _checked_model_set(model_set, M, K)
+        C, L, mu, w = _checked_chains(M, xs.shape[1], chain_len, coupling, link_weights)
+        gap = ~np.isfinite(obs[model_set]).any(axis=1)
+        dev = default_device()
+        sets = _sets_on(curves, obs, sigma, dev)
+        at = torch.from_numpy(model_set).to(dev)
+        fields, more, timings = self._descend_section(
+            sets.table, lambda c, dcdp, chain: lm_normal_sets(c, dcdp, chain, sets, at), xs,
+            torch.from_numpy(gap).to(dev), torch.from_numpy(mu).to(dev), torch.from_numpy(w).to(dev), L, maxiter, lam0,
+            tol, profile)
+        return SectionResult(*fields, timings=timings, model_set=model_set, n_set=K, n_chain=C, chain_len=L,
+                             coupling=mu, link_weights=w, gap=gap, **more)
 
 
 # ------------------------------------------------------------------------------------------------- sensitivities

@@ -656,6 +656,36 @@ int dvh_lm_normal_sets(const double* c, const double* dcdp, const double* chain,
 int dvh_lm_solve(const double* H, const double* g, const double* lambda, const int32_t* free_mask, int32_t n_model,
                  int32_t n_param, double* out_delta, int32_t* out_status, void* stream);
 
+/* The damped step of chains of models tied by first differences, one workgroup per chain.  Rows c chain_len + k,
+ * k = 0 .. chain_len - 1, of H, g and u [n_model = n_chain chain_len] are the positions of chain c; u is each row's
+ * point in the unit cube.  Over the free parameters of all positions of a chain the system is block tridiagonal:
+ *   A_k = H_k + lambda_c diag(d_k) + (w_{k-1} + w_k) diag(mu)   on the diagonal, d_k as in dvh_lm_solve per row,
+ *   B_k = -w_k diag(mu)                                         between positions k and k + 1,
+ *   r_k = -(g_k + q_k),  q_k = mu [ w_{k-1} (u_k - u_{k-1}) - w_k (u_{k+1} - u_k) ]
+ * with w = link [n_chain][chain_len - 1] and mu [n_param], both >= 0 (not checked: device data); a term whose
+ * neighbour does not exist is left out.  Block Cholesky in float64 along the chain, every inner product one sequential
+ * sum; the factors of every position go through workspace (dvh_lm_solve_chain_workspace(n_model, n_param) bytes,
+ * 8-byte aligned) for the back sweep.  lambda is [n_chain], free_mask int32 [n_param].
+ *   out_delta  [n_model][n_param]  the step; exactly 0 for a parameter that is not free
+ *   out_status [n_chain] int32     0, or 2: a pivot that is not positive and finite at any position, a step that is
+ *                                  not finite, or a stretch of positions between cut links (w = 0) or chain ends
+ *                                  without a positive H_kk (coupling alone is singular); delta is then 0 in every
+ *                                  row of that chain, and of that chain only
+ * With chain_len = 1, or with mu or link all 0, out_delta is dvh_lm_solve's with lambda_c at each row, bit for bit.
+ * -2: NULL pointers, n_chain < 0, chain_len < 1, n_param < 1.  -4: n_param > 96.  n_chain = 0 returns 0 without a
+ * launch.  dvh_lm_solve_chain_workspace returns 0 for arguments that dvh_lm_solve_chain refuses. */
+int64_t dvh_lm_solve_chain_workspace(int32_t n_model, int32_t n_param);
+int dvh_lm_solve_chain(const double* H, const double* g, const double* u, const double* lambda,
+                       const int32_t* free_mask, const double* mu, const double* link, int32_t n_chain,
+                       int32_t chain_len, int32_t n_param, void* workspace, double* out_delta, int32_t* out_status,
+                       void* stream);
+
+/* dvh_lm_solve_chain on the CPU over host memory (workspace included), as the host entries below. */
+int dvh_lm_solve_chain_host(const double* H, const double* g, const double* u, const double* lambda,
+                            const int32_t* free_mask, const double* mu, const double* link, int32_t n_chain,
+                            int32_t chain_len, int32_t n_param, void* workspace, double* out_delta,
+                            int32_t* out_status);
+
 /* dvh_lm_normal, dvh_lm_normal_sets and dvh_lm_solve on the CPU over host memory, from the same header
  * (csrc/refine.h) and in the same order of operations; no device is touched.  They pin the arithmetic where there is no
  * GPU and are no fallback: nothing refines models with them.  Arguments, outputs and return codes as above. */
