@@ -51,6 +51,10 @@ SIGNATURES = {
     "dvh_ridge": [_p, _i64, _i32, _i32, _i32, _i32, _i32, _p, _i32, _f64, _f64, _p, _p, _i32, _p, _p, _p, _p],
     "dvh_slant_ridge": [_p, _i32, _i32, _i32, _p, _p, _i32, _f64, _i32, _i32, _p, _i32, _i32, _f64, _f64, _p, _p, _i32,
                         _p, _p, _p, _p],
+    "dvh_hilbert_rows": [_p, _i64, _i32, _i32, _p, _p, _p],
+    "dvh_hilbert_rows_host": [_p, _i64, _i32, _i32, _p, _p],
+    "dvh_select_pws": [_p, _p, _i64, _i64, _p, _p, _p, _i32, _f32, _p, _i64, _p],
+    "dvh_select_pws_host": [_p, _p, _i64, _i64, _p, _p, _p, _i32, _f32, _p, _i64],
     "dvh_sosfiltfilt_workspace": [_i64, _i32, _i32, _i32],
     "dvh_sosfiltfilt": [_p, _i32, _i64, _i64, _i32, _p, _i32, _i32, _p, _p, _p],
     "dvh_sosfiltfilt_plan_bytes": [_i32],

@@ -199,32 +199,52 @@ def save_disp_imgs(windows, weight, min_win, x, start_x, end_x, offset, fig_dir,
 
 
 def bootstrap_disp(surf_wins, bt_size, bt_times, sigma, pivot, start_x, end_x, ref_freq_idx, freq_lb, freq_up,
-                   ref_vel, transform="fk", walk=None):
+                   ref_vel, transform="fk", walk=None, stack="linear", pws_power=2.0):
     """apis/imaging_classes.py:8-48: bt_times resamples of random.sample(range(1, n), bt_size)
     windows -> class-stack VSG -> compute_disp_image(end_x=0, start_x=-150) -> one ridge per mode.
     Same draws (Python ``random``), same return value: (ridge_vel[mode][resample], freqs).  All
     resamples run as one batch on the device (das_diff_veh_amd.bootstrap).  ``transform`` selects the image the ridges
     are walked on: "fk" (map_fv, the reference's) or "slant" (the phase-shift transform, compute_disp_image(...,
     transform="slant")); with "slant", ``walk`` = "fused" / "image" selects the kernel (bootstrap.bootstrap_ridges; the
-    results are the same).  A pair that does not exist raises ValueError before any device work."""
+    results are the same).  A pair that does not exist raises ValueError before any device work.  ``stack`` = "pws"
+    stacks every resample by the phase-weighted stack with ``pws_power`` (0, or at least 1; bootstrap.check_stack)
+    instead of the reference's mean, "linear"."""
     from .. import bootstrap as bt
     bt.check_transform(transform, walk)
+    bt.check_stack(stack, pws_power)
     cache = bt.GatherCache(surf_wins, pivot, start_x, end_x)
     sels = bt.draw(len(surf_wins), bt_size, bt_times)
     per_mode = bt.bootstrap_ridges(cache, sels, sigma, ref_freq_idx, freq_lb, freq_up, ref_vel, transform=transform,
-                                   walk=walk)
+                                   walk=walk, stack=stack, power=pws_power)
     return [list(r) for r in per_mode], bt.FREQS.copy()
 
 
 def convergence_test(max_sample_num, windows, bt_times, sigma, x0, start_x, end_x, ref_freq_idx, freq_lb, freq_ub,
-                     vel_ref, transform="fk", walk=None):
+                     vel_ref, transform="fk", walk=None, stack="linear", pws_power=2.0):
     """imaging_diff_speed.ipynb#cell30: for bt_size = 1..max_sample_num, the summed per-frequency
     std of the bootstrap ridges -> [n_modes, max_sample_num].  The gathers are computed once for all
     60 x bt_times resamples (the notebook recomputes them per resample); draws as the notebook's; all
     resamples imaged in one batch (das_diff_veh_amd.bootstrap.convergence).  ``transform`` and ``walk`` as
-    bootstrap_disp takes them."""
+    bootstrap_disp takes them, ``stack`` and ``pws_power`` too."""
     from .. import bootstrap as bt
     bt.check_transform(transform, walk)
+    bt.check_stack(stack, pws_power)
     cache = bt.GatherCache(windows, x0, start_x, end_x)
     return bt.convergence(cache, max_sample_num, bt_times, sigma, ref_freq_idx, freq_lb, freq_ub, vel_ref,
-                          transform=transform, walk=walk)
+                          transform=transform, walk=walk, stack=stack, power=pws_power)
+
+
+def phase_weighted_gather(windows, pivot, start_x, end_x, power=2.0, wlen=2, include_other_side=True):
+    """The phase-weighted stack (Schimmel & Paulssen 1997) of the windows' virtual shot gathers: the linear stack
+    get_images forms, multiplied sample by sample by the coherence of the passes' instantaneous phases to ``power``
+    (0, or at least 1).  All windows in order over all gather rows, from per-pass gathers computed once
+    (bootstrap.GatherCache, dvh_hilbert_rows, dvh_select_pws).  Returns a VirtualShotGather on the first window's
+    axes; compute_disp_image works on it with either transform."""
+    from .. import bootstrap as bt
+    power = bt.check_stack("pws", power)
+    windows = list(windows)
+    cache = bt.GatherCache(windows, pivot, start_x, end_x, wlen=wlen, include_other_side=include_other_side)
+    stack = cache.phase_weighted_stack(power)
+    w = int(cache.w_of[0])
+    xcf = stack[0, :, :w].detach().to("cpu").numpy().astype(np.float64)
+    return VirtualShotGather._from_arrays(windows[0], xcf, cache.gx, cache.gt)

@@ -17,6 +17,10 @@ the f-k image: either through the resamples' images and ``dvh_ridge`` (walk="ima
 through ``dvh_slant_ridge`` (walk="fused"), whose walk computes the steering sums of the velocities it compares from
 the stacks' spectra and forms no image (``plan_ridges``, ``slant_ridges``).
 
+``stack="pws"`` replaces the mean of step 2 by the phase-weighted stack (Schimmel & Paulssen 1997): the mean times the
+coherence of the drawn passes' instantaneous phases to ``power``, from the analytic signal of the cached rows
+(``GatherCache.analytic``: ``dvh_hilbert_rows`` once per cache; ``dvh_select_pws`` per call).  Steps 3 and 4 are the same.
+
 Random draws use Python's ``random`` exactly as the reference does (``random.sample(range(1, n), k)``,
 index 0 never drawn), so seeding ``random`` reproduces the reference's resamples.
 """
@@ -138,6 +142,24 @@ def check_transform(transform, walk=None):
     return SLANT_WALK if walk is None else walk
 
 
+STACKS = ("linear", "pws")
+
+
+def check_stack(stack, power=2.0):
+    """The power of a (stack, power) pair as a float -- "linear": the mean sum(images) / len(images); "pws": the
+    phase-weighted stack lin * c^power (dvh_select_pws), power 0 or at least 1 -- or ValueError for a stack that does
+    not exist or a power the kernel refuses.  No device work."""
+    if stack not in STACKS:
+        raise ValueError(f"stack must be 'linear' or 'pws', not {stack!r}")
+    try:
+        p = float(power)
+    except (TypeError, ValueError):
+        raise ValueError(f"power must be a number, not {power!r}") from None
+    if not (p == 0.0 or 1.0 <= p <= float(np.finfo(np.float32).max)):
+        raise ValueError(f"power must be 0 or a finite value of at least 1, not {power!r}")
+    return p
+
+
 def _side_stream(device, k):
     """The k-th side stream of a device (created once)."""
     key = (str(device), k)
@@ -190,6 +212,7 @@ class GatherCache:
             self._gt_of.setdefault(g.w, g.gather_t_axis)
         self.n = len(windows)
         self._disp = {}
+        self._H = None
 
     @classmethod
     def from_device(cls, data, x_axis, t_axis, trk_x, trk_t, trk_len, pivot, start_x, end_x, wlen=2,
@@ -214,6 +237,7 @@ class GatherCache:
         self.W = self.plan.w
         self._gt_of = {self.plan.w: self.gt}
         self._disp = {}
+        self._H = None
         return self
 
     def disp_plan(self, start_x=-150, end_x=0, freqs=FREQS, vels=VELS, w=None):
@@ -288,9 +312,43 @@ class GatherCache:
             out[rt] = fv
         return out
 
-    def resample_stacks(self, sel, start_x=-150, end_x=0, out=None):
-        """Mean gathers over the disp rows for every draw: sel [B, k] pass indices -> [B, nch, w] (into
-        ``out``, a contiguous [B, nch, w] float32 device tensor, when given)."""
+    def analytic(self):
+        """H [n, R, W]: the imaginary part of every cached row's analytic signal (dvh_hilbert_rows), each pass over
+        its own w_of lags and 0 beyond, computed on the first call and kept."""
+        if self._H is None:
+            from .device import upload
+            G = self.G.contiguous()
+            H = torch.empty_like(G)
+            R = int(G.shape[1])
+            row_len, = upload([np.repeat(self.w_of, R).astype(np.int32)], self.device)
+            _lib.call("dvh_hilbert_rows", _lib.ptr(G), self.W, self.n * R, self.W, _lib.ptr(row_len), _lib.ptr(H),
+                      _lib.stream_of(self.device))
+            self._H = H
+        return self._H
+
+    def _select_pws(self, s, e, sel_t, off_t, cnt_t, B, power, out):
+        """dvh_select_pws of B draws over gather rows s..e into out [B, e + 1 - s, W]."""
+        w, R = self.W, self.plan.R
+        rows = (e + 1 - s) * w
+        _lib.call("dvh_select_pws", _lib.ptr(self.G[:, s:e + 1, :]), _lib.ptr(self.analytic()[:, s:e + 1, :]), R * w,
+                  rows, _lib.ptr(sel_t), _lib.ptr(off_t), _lib.ptr(cnt_t), B, power, _lib.ptr(out), rows,
+                  _lib.stream_of(self.device))
+        return out
+
+    def phase_weighted_stack(self, power=2.0):
+        """The phase-weighted stack of all passes in order over all R gather rows: [1, R, W]."""
+        from .device import upload
+        power = check_stack("pws", power)
+        out = torch.empty((1, self.plan.R, self.W), dtype=torch.float32, device=self.device)
+        sel_t, off_t, cnt_t = upload([np.arange(self.n, dtype=np.int32), np.zeros(1, np.int32),
+                                      np.full(1, self.n, dtype=np.int32)], self.device)
+        return self._select_pws(0, self.plan.R - 1, sel_t, off_t, cnt_t, 1, power, out)
+
+    def resample_stacks(self, sel, start_x=-150, end_x=0, out=None, stack="linear", power=2.0):
+        """Stacked gathers over the disp rows for every draw: sel [B, k] pass indices -> [B, nch, w] (into
+        ``out``, a contiguous [B, nch, w] float32 device tensor, when given).  ``stack``: "linear" (the mean) or "pws"
+        (the phase-weighted stack with ``power``, check_stack)."""
+        power = check_stack(stack, power)
         sel = np.asarray(sel, dtype=np.int32)
         if sel.ndim != 2 or sel.size == 0 or sel.min() < 0 or sel.max() >= self.n:
             raise ValueError("selections must be [B, k] pass indices")
@@ -301,18 +359,25 @@ class GatherCache:
             out = torch.empty((B, e + 1 - s, w), dtype=torch.float32, device=self.device)
         elif tuple(out.shape) != (B, e + 1 - s, w) or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous float32 [{B}, {e + 1 - s}, {w}] tensor")
+        if stack == "pws":
+            from .device import upload
+            sel_t, off_t, cnt_t = upload([sel.reshape(-1), np.arange(B, dtype=np.int32) * k,
+                                          np.full(B, k, dtype=np.int32)], self.device)
+            return self._select_pws(s, e, sel_t, off_t, cnt_t, B, power, out)
         sel_t = torch.as_tensor(sel, device=self.device)
         base = self.G[:, s:e + 1, :]
         _lib.call("dvh_select_mean", _lib.ptr(base), R * w, (e + 1 - s) * w, _lib.ptr(sel_t), B, k, _lib.ptr(out),
                   (e + 1 - s) * w, _lib.stream_of(self.device))
         return out
 
-    def resample_stacks_sizes(self, sels, start_x=-150, end_x=0, out=None):
+    def resample_stacks_sizes(self, sels, start_x=-150, end_x=0, out=None, stack="linear", power=2.0):
         """resample_stacks of several draw sets (sels: list of [B_k, k] arrays, e.g. one per bootstrap size) into
         consecutive rows of one [sum B_k, nch, w] buffer: every selection, with each resample's offset and size,
         crosses to the device in ONE asynchronous copy (device.upload) and all resamples are one
-        dvh_select_mean_var launch (60 launches of 30 resamples each were latency-bound: 0.94 ms)."""
+        dvh_select_mean_var launch (60 launches of 30 resamples each were latency-bound: 0.94 ms), or with
+        stack="pws" one dvh_select_pws launch."""
         from .device import upload
+        power = check_stack(stack, power)
         sels = [np.asarray(x, dtype=np.int32) for x in sels]
         if not sels or any(x.ndim != 2 or x.size == 0 for x in sels):
             raise ValueError("selections must be [B, k] pass indices")
@@ -330,16 +395,20 @@ class GatherCache:
         cnt = np.concatenate([np.full(x.shape[0], x.shape[1], dtype=np.int32) for x in sels])
         off = np.concatenate([[0], np.cumsum(cnt[:-1], dtype=np.int64)]).astype(np.int32)
         sel_t, off_t, cnt_t = upload([flat, off, cnt], self.device)
+        if stack == "pws":
+            return self._select_pws(s, e, sel_t, off_t, cnt_t, B, power, out)
         base = self.G[:, s:e + 1, :]
         _lib.call("dvh_select_mean_var", _lib.ptr(base), R * w, rows, _lib.ptr(sel_t), _lib.ptr(off_t), _lib.ptr(cnt_t),
                   B, _lib.ptr(out), rows, _lib.stream_of(self.device))
         return out
 
-    def resample_images(self, sel, start_x=-150, end_x=0, transform="fk"):
+    def resample_images(self, sel, start_x=-150, end_x=0, transform="fk", stack="linear", power=2.0):
         """f-v images [B, Nvel, Nfreq] of every draw's stack (compute_disp_image(end_x, start_x, transform))."""
         check_transform(transform)
+        check_stack(stack, power)
         sel = np.asarray(sel, dtype=np.int32)
-        return self.images_of(self.resample_stacks(sel, start_x, end_x), sel[:, 0], start_x, end_x, transform)
+        return self.images_of(self.resample_stacks(sel, start_x, end_x, stack=stack, power=power), sel[:, 0], start_x,
+                              end_x, transform)
 
 
 def plan_ridges(stacks, plan: SlantPlan, freq_lb, freq_ub, ref_freq_idx, sigma, vel_max, ref_vel,
@@ -452,18 +521,20 @@ def _band_ref(ref_freq_idx, freq_lb):
 
 
 def bootstrap_ridges(cache: GatherCache, sels, sigma, ref_freq_idx, freq_lb, freq_up, ref_vel, start_x=-150,
-                     end_x=0, transform="fk", walk=None):
+                     end_x=0, transform="fk", walk=None, stack="linear", power=2.0):
     """Ridge velocities per mode for draws ``sels`` [B, k]: list over modes of [B, n_band] arrays.  ``transform``
     selects the image the ridges are walked on ("fk": map_fv, "slant": the phase-shift transform); with "slant",
     ``walk`` selects how: "image" forms the images and walks them (dvh_ridge), "fused" computes the compared values
-    inside the walk (dvh_slant_ridge) with the same results, None takes SLANT_WALK."""
+    inside the walk (dvh_slant_ridge) with the same results, None takes SLANT_WALK.  ``stack`` and ``power`` select the
+    stack of every draw (check_stack): the mean, or the phase-weighted stack."""
     walk = check_transform(transform, walk)
+    check_stack(stack, power)
     if walk == "fused":
         sels = np.asarray(sels, dtype=np.int32)
         refs = [_band_ref(ref_freq_idx[m], freq_lb[m]) for m in range(len(freq_lb))]
-        return slant_ridges(cache, cache.resample_stacks(sels, start_x, end_x), sels[:, 0], freq_lb, freq_up, refs,
-                            sigma, 800, ref_vel, start_x, end_x)
-    fv = cache.resample_images(sels, start_x, end_x, transform)
+        return slant_ridges(cache, cache.resample_stacks(sels, start_x, end_x, stack=stack, power=power), sels[:, 0],
+                            freq_lb, freq_up, refs, sigma, 800, ref_vel, start_x, end_x)
+    fv = cache.resample_images(sels, start_x, end_x, transform, stack, power)
     out = []
     for m in range(len(freq_lb)):
         out.append(ridges(fv, FREQS, VELS, freq_lb[m], freq_up[m], ref_freq_idx=_band_ref(ref_freq_idx[m], freq_lb[m]),
@@ -472,7 +543,7 @@ def bootstrap_ridges(cache: GatherCache, sels, sigma, ref_freq_idx, freq_lb, fre
 
 
 def convergence(cache: GatherCache, max_size, bt_times, sigma, ref_freq_idx, freq_lb, freq_up, ref_vel, start_x=-150,
-                end_x=0, rand=random, phases=None, transform="fk", walk=None):
+                end_x=0, rand=random, phases=None, transform="fk", walk=None, stack="linear", power=2.0):
     """The notebooks' convergence_test (imaging_diff_speed.ipynb#cell30) on a gather cache: for bt_size =
     1..max_size, bt_times resamples (the same random.sample draws in the same order as the notebook's
     per-size bootstrap_disp calls), their ridges per mode, and the summed per-frequency std -> [n_modes,
@@ -480,8 +551,12 @@ def convergence(cache: GatherCache, max_size, bt_times, sigma, ref_freq_idx, fre
     into one buffer, one tdft / fk / f-v launch each, one ridge launch per mode), so the host synchronises
     once per mode instead of once per (size, mode).  ``phases`` (optional dict) receives torch events
     around the resample / dispersion / ridge parts for timing.  ``transform`` and ``walk`` as bootstrap_ridges takes
-    them; the fused walk forms no images (its "disp1" event follows "select1" at once)."""
+    them; the fused walk forms no images (its "disp1" event follows "select1" at once).  ``stack`` and ``power`` as
+    bootstrap_ridges takes them; the analytic signal of the cache is formed before the "select0" event."""
     walk = check_transform(transform, walk)
+    check_stack(stack, power)
+    if stack == "pws":
+        cache.analytic()
     t_draw = time.perf_counter()
     sels = draw_sizes(cache.n, range(1, max_size + 1), bt_times, rand)
     if phases is not None:
@@ -490,7 +565,7 @@ def convergence(cache: GatherCache, max_size, bt_times, sigma, ref_freq_idx, fre
     ev = (lambda name: phases.setdefault(name, torch.cuda.Event(enable_timing=True)).record()) if phases is not None \
         else (lambda name: None)
     ev("select0")
-    stacks = cache.resample_stacks_sizes(sels, start_x, end_x)
+    stacks = cache.resample_stacks_sizes(sels, start_x, end_x, stack=stack, power=power)
     ev("select1")
     first = np.concatenate([x[:, 0] for x in sels])
     refs = [_band_ref(ref_freq_idx[m], freq_lb[m]) for m in range(len(freq_lb))]

@@ -278,6 +278,45 @@ int dvh_slant_ridge(const double* D, int32_t B, int32_t n_row, int32_t n_fb, con
                     double sigma, double vel_max, const double* vref, const double* sg, int32_t sgl, double* out,
                     int32_t* status, double* picks, void* stream);
 
+/* ---------------------------------------------------------------- phase-weighted stack (Schimmel & Paulssen 1997)
+ * out = lin * c^power per sample, lin the linear stack of a draw and c = |sum_j (g_j + i h_j) / |g_j + i h_j|| / m the
+ * coherence of the drawn passes' instantaneous phases ("Phase-weighted stack"). */
+#define DVH_PWS_MAX_LEN 1024
+
+/* H[r][t] = imag(scipy.signal.hilbert(X[r][:N]))[t] for t < N = row_len[r] (row_len null: N = W), 0 for N <= t < W:
+ * n_row rows of float32, row_stride >= W floats apart in X and in H alike; row_len[n_row] a device array with
+ * 0 <= row_len[r] <= W (a length outside is clamped).  The circular convolution with the transform's taps, summed in
+ * float64 in ascending tap order and rounded once.  A row with a non-finite sample is NaN at every t < N.
+ * -2 for a null X or H, a negative count or row_stride < W; -4 for W > DVH_PWS_MAX_LEN; n_row == 0 or W == 0 return 0
+ * and write nothing. */
+int dvh_hilbert_rows(const float* X, int64_t row_stride, int32_t n_row, int32_t W, const int32_t* row_len, float* H,
+                     void* stream);
+
+/* Host function: dvh_hilbert_rows by the same arithmetic over host memory; a row_len[r] outside [0, W] is -2. */
+int dvh_hilbert_rows_host(const float* X, int64_t row_stride, int32_t n_row, int32_t W, const int32_t* row_len,
+                          float* H);
+
+/* The phase-weighted stack of dvh_select_mean_var's draws: G, pass_stride, K, sel, off, cnt, B, out and out_stride as
+ * there, H (dvh_hilbert_rows of G's rows) laid out as G.  Float32, three sums in selection order: the linear sum by
+ * dvh_select_mean's adds, and the real and imaginary parts of the phasors g / |a|, h / |a| with 1 / |a| =
+ * 1 / sqrtf(g*g + h*h), 0 where that is not positive.  power 0 gives the linear stack bit for bit; 1 and 2 multiply by
+ * c and c * c, any other by powf(c, power).  -2 for a null pointer, a negative count or a power that is negative,
+ * non-finite or inside (0, 1); -4 for B > 65535; B == 0 or K == 0 return 0 and write nothing.  cnt is read on the
+ * device only, so this entry cannot refuse cnt[b] < 1: such a resample reads no pass; cnt[b] == 0 comes out NaN
+ * (-0 / 0) and a negative cnt[b] comes out 0.
+ * Amplitudes: g*g + h*h is formed in float32, so the phasor is exact to its roundings for 1.1e-19 <= |g + i h| <=
+ * 1.8e19.  Above, the sum of squares overflows, 1 / |a| is 0 and the sample drops out of c (not out of lin or m); below,
+ * it is subnormal and the phase loses precision, and under 2.6e-23 it is 0 and the sample counts as dead.  Gathers
+ * outside that range want scaling by a power of two first: lin scales with it, c does not change. */
+int dvh_select_pws(const float* G, const float* H, int64_t pass_stride, int64_t K, const int32_t* sel,
+                   const int32_t* off, const int32_t* cnt, int32_t B, float power, float* out, int64_t out_stride,
+                   void* stream);
+
+/* Host function: dvh_select_pws by the same arithmetic over host memory; a cnt[b] < 1 is -2 and nothing is written. */
+int dvh_select_pws_host(const float* G, const float* H, int64_t pass_stride, int64_t K, const int32_t* sel,
+                        const int32_t* off, const int32_t* cnt, int32_t B, float power, float* out,
+                        int64_t out_stride);
+
 /* ---------------------------------------------------------------- preprocessing
  * dtype: 0 float32, 1 float64; data modified in place. */
 
