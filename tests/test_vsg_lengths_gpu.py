@@ -1,7 +1,9 @@
 """GPU parity of the VSG kernels at every correlation window length w the dispatch serves, against the float64
 oracle: the six engines of the engine table (engine_for, dvh_vsg.hip) at their first, last and odd w, through the
 per-pass gathers, the plain and validated class stacks, other sub-window counts, single samples at the edges of the
-load masks, and the error beyond w = 1024.
+load masks, and the error beyond w = 1024.  Besides the gather-maximum tolerance every comparison holds the
+kernels to the per-lag float32 error budget of tests/vsg_budget.py (row by row and lag by lag, C calibrated on the
+host against a float32 restatement of the oracle).
 
 Passes: synth_pass, 24 channels x 6 500 samples (610 m first channel), pivot 700, gather rows 620-780 m (19 rows: 10
 below the pivot row, 8 above), delta_t = 1.  6 500 samples, not the 5 500 of the other VSG tests: at w ~ 1000 the two
@@ -101,29 +103,39 @@ def _plan(case, flags, mult=2, idx=range(N_PASS)):
     return geoms, plan
 
 
-def _oracle(case, flags, mult, i, data=None):
-    """Oracle gather of pass i (cached per (case, flags, sub-window count, pass) for the unmodified pass)."""
-    from oracle import vsg as ovsg
+def _budget(case, flags, mult, i, data=None):
+    """(oracle gather, per-lag budget) of pass i (cached per (case, flags, sub-window count, pass) for the unmodified
+    pass)."""
+    from tests import vsg_budget
     key = ("ref", case, tuple(sorted(flags.items())), mult, i)
     if data is None and key in _cache:
         return _cache[key]
     p = _passes(case[1])[i]
     o = dict(data=p["host"] if data is None else data, x_axis=p["x_axis"], t_axis=p["t_axis"],
              veh_state_x=p["veh_state_x"], veh_state_t=p["veh_state_t"])
-    with np.errstate(all="ignore"):
-        ref = ovsg.virtual_shot_gather(o, **_kw(case, flags, mult))[0]
+    ref = vsg_budget.budget_gather(o, **_kw(case, flags, mult))
     if data is None:
         _cache[key] = ref
     return ref
 
 
-def _class_refs(case, flags, mult, replace=None):
-    """Oracle class means of SLOTS ([2, R, w]); replace: {pass: oracle gather of its modified data}."""
+def _oracle(case, flags, mult, i, data=None):
+    return _budget(case, flags, mult, i, data)[0]
+
+
+def _stack_budget(per):
+    """(oracle.vsg.stack of the gathers, budget, float32 accumulation term) of [(gather, budget)]."""
     from oracle import vsg as ovsg
-    refs = [(replace or {}).get(i, None) for i in range(N_PASS)]
-    refs = [_oracle(case, flags, mult, i) if r is None else r for i, r in enumerate(refs)]
+    from tests import vsg_budget
+    _, beta, extra = vsg_budget.stack_budget([r for r, _ in per], [b for _, b in per])
     with np.errstate(all="ignore"):
-        return [ovsg.stack([refs[i] for i in range(N_PASS) if SLOTS[i] == s]) for s in range(2)]
+        return ovsg.stack([r for r, _ in per]), beta, extra
+
+
+def _class_refs(case, flags, mult):
+    """Oracle class means of SLOTS with their budgets: [(ref, beta, extra)] per class."""
+    per = [_budget(case, flags, mult, i) for i in range(N_PASS)]
+    return [_stack_budget([per[i] for i in range(N_PASS) if SLOTS[i] == s]) for s in range(2)]
 
 
 def row_rel_err(got, ref):
@@ -138,14 +150,18 @@ def row_rel_err(got, ref):
     return worst
 
 
-def _check(tag, got, ref, flags):
+def _check(tag, got, ref, flags, case=None, beta=None, extra=0.0):
     """Gather parity, and per-row parity where every row is normalised (a wrong far row cannot hide under a strong
-    near one); prints both figures."""
+    near one); prints both figures.  Then the per-lag budget (tests/vsg_budget.py), which holds every row to its own
+    scale with or without normalisation; every caller in this module passes it (case, beta; extra for a stack)."""
+    from tests import vsg_budget
     err, rerr = gio.gather_rel_err(got, ref), row_rel_err(got, ref)
     print(f"{tag}: err {err:.3e}, per-row {rerr:.3e}")
     assert err < TOL, (tag, err)
     if flags.get("norm", True):
         assert rerr < TOL, (tag, rerr)
+    if beta is not None:
+        vsg_budget.assert_within_budget(tag, got, ref, beta, case[3], flags, extra, w=case[2])
     return err
 
 
@@ -163,7 +179,8 @@ def _run_gathers(device, case, flags, mult=2):
     got = vsg.vsg_gathers(_windows(device, case[1]), plan).double().cpu().numpy()
     assert got.shape == (N_PASS, R, case[2])
     for i in range(N_PASS):
-        _check(f"gathers w={case[2]} x{mult} {flags} pass {i}", got[i], _oracle(case, flags, mult, i), flags)
+        ref, beta = _budget(case, flags, mult, i)
+        _check(f"gathers w={case[2]} x{mult} {flags} pass {i}", got[i], ref, flags, case, beta)
 
 
 def _run_stack(device, case, flags, mult=2):
@@ -171,8 +188,8 @@ def _run_stack(device, case, flags, mult=2):
     _, plan = _plan(case, flags, mult)
     got = vsg.vsg_stack(_windows(device, case[1]), plan, _sched()).double().cpu().numpy()
     assert got.shape == (2, R, case[2])
-    for s, ref in enumerate(_class_refs(case, flags, mult)):
-        _check(f"stack w={case[2]} x{mult} {flags} class {s}", got[s], ref, flags)
+    for s, (ref, beta, extra) in enumerate(_class_refs(case, flags, mult)):
+        _check(f"stack w={case[2]} x{mult} {flags} class {s}", got[s], ref, flags, case, beta, extra)
 
 
 @pytest.mark.parametrize("case", TABLE, ids=CASE_IDS)
@@ -218,7 +235,7 @@ def test_validated_stack(device, case, flags):
     refs = _class_refs(case, flags, 2)
     got = vsg.vsg_stack_validated(wins, plan, _sched()).double().cpu().numpy()
     for s in range(2):
-        _check(f"validated w={case[2]} {flags} clean class {s}", got[s], refs[s], flags)
+        _check(f"validated w={case[2]} {flags} clean class {s}", got[s], refs[s][0], flags, case, *refs[s][1:])
     # pass 3 (the five-pass class 1): channel 23 lies beyond end_x; pass 1 (the one-pass class 0): all zero
     assert plan.geoms[3].end_idx <= N_CH - 1
     for p, kind in ((3, "nan"), (1, "zero")):
@@ -230,7 +247,8 @@ def test_validated_stack(device, case, flags):
         got = vsg.vsg_stack_validated(data, plan, _sched()).double().cpu().numpy()
         bad, good = int(SLOTS[p]), 1 - int(SLOTS[p])
         assert np.isnan(got[bad]).all(), (case, kind)
-        _check(f"validated w={case[2]} {flags} {kind} in pass {p}, class {good}", got[good], refs[good], flags)
+        _check(f"validated w={case[2]} {flags} {kind} in pass {p}, class {good}", got[good], refs[good][0], flags, case,
+               *refs[good][1:])
 
 
 @pytest.mark.parametrize("mult", [1, 3])
@@ -279,7 +297,7 @@ def test_single_sample_receiver_slices(device, case, flags):
             data[1, geo.start_idx + row, a + pos] = 40.0
             rows.append(row)
     host1 = data[1].double().cpu().numpy()
-    ref1 = _oracle(case, flags, 1, 1, host1)
+    ref1, beta1 = _budget(case, flags, 1, 1, host1)
     blind = host1.copy()
     blind[host1 == 40.0] = 0.0
     assert (host1 == 40.0).sum() == len(rows)
@@ -289,11 +307,13 @@ def test_single_sample_receiver_slices(device, case, flags):
     print(f"w={w} {flags}: positions {positions}, the lone samples move every row by >= {moved:.3e}")
     assert moved > 10 * TOL
     got = vsg.vsg_gathers(data, plan).double().cpu().numpy()
-    _check(f"single samples w={w} {flags} gathers", got[1], ref1, flags)
+    _check(f"single samples w={w} {flags} gathers", got[1], ref1, flags, case, beta1)
     sched = vsg.StackSchedule(np.zeros(len(idx), np.int64), 1, chunk=4)
     got = vsg.vsg_stack(data, plan, sched).double().cpu().numpy()[0]
-    refs = [ref1 if i == 1 else _oracle(case, flags, 1, i) for i in idx]
-    _check(f"single samples w={w} {flags} stack", got, ovsg.stack(refs), flags)
+    per = [(ref1, beta1) if i == 1 else _budget(case, flags, 1, i) for i in idx]
+    refs = [r for r, _ in per]
+    ref, beta, extra = _stack_budget(per)
+    _check(f"single samples w={w} {flags} stack", got, ref, flags, case, beta, extra)
     moved = gio.gather_rel_err(ovsg.stack([refb if i == 1 else r for i, r in zip(idx, refs)]), ovsg.stack(refs))
     assert moved > 10 * TOL
 
@@ -327,11 +347,12 @@ def test_samples_next_to_the_slices_are_not_read(device, case, flags):
                     n_spike += 1
     assert n_spike >= 2 * sides * (R - 1) - 4
     host1 = data[1].double().cpu().numpy()
-    ref1 = _oracle(case, flags, 1, 1, host1)
+    ref1, beta1 = _budget(case, flags, 1, 1, host1)
     got = vsg.vsg_gathers(data, plan).double().cpu().numpy()
-    _check(f"spikes beside the slices w={w} {flags} gathers", got[1], ref1, flags)
+    _check(f"spikes beside the slices w={w} {flags} gathers", got[1], ref1, flags, case, beta1)
     got = vsg.vsg_stack(data, plan, vsg.StackSchedule(np.zeros(2, np.int64), 1, chunk=2)).double().cpu().numpy()[0]
-    _check(f"spikes beside the slices w={w} {flags} stack", got, ovsg.stack([_oracle(case, flags, 1, 0), ref1]), flags)
+    ref, beta, extra = _stack_budget([_budget(case, flags, 1, 0), (ref1, beta1)])
+    _check(f"spikes beside the slices w={w} {flags} stack", got, ref, flags, case, beta, extra)
 
 
 def test_unsupported_length_raises(device):
